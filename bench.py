@@ -8,10 +8,17 @@ splitmix64(flowId) mod N; every rank owns its shard's rules and decides the
 requests routed to it (no data-path collective; "weak" scaling: each rank sees
 a global batch of N * 2^24 requests at lambda = N * 1e8 requests per virtual
 second, of which ~2^24 are its own).  A step = one DefaultTokenService batch
-(sga_request_tokens_device) over one pre-generated, HBM-resident batch.
+(sga_request_tokens_device) over one pre-generated, HBM-resident batch.  At most RING_BATCHES distinct
+batches are generated, so HBM use does not grow with --steps: a longer run goes round them, each pass
+at its own, later virtual time (`config.distinct_batches` in the line).
 
-Prints ONE JSON line on rank 0 (the driver's contract) with `roofline` and
-`cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (the driver's contract).  A plain run sets up, warms up, times the
+steps and prints the line with its `roofline` object (computed from the timed steps themselves).
+`--full` adds the legs that take runs of their own after the timed loop: the oracle check of the first two
+timed batches (`parity_sample`), the host-buffer batches (`end_to_end_host_buffers`), and the CPU
+baseline with the host router / wire decoder timings (`cpu_baseline`, `host_router`); `--no-cpu`,
+`--no-e2e` and `--no-parity` switch single legs off again.  `--dump-outputs DIR` writes what the last
+timed step returned (dump_outputs in bench_local.py).
 """
 import argparse
 import ctypes as C
@@ -30,7 +37,8 @@ N_RULES = 1_000_000
 LAMBDA_PER_GPU = 100_000_000
 E_IN, E_OUT, S_FLOW = 12, 8, 704  # token request 12 B, token result 8 B, cluster flow 704 B
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: 8.0 TB/s spec
-E2E_BATCHES = 6                   # host-buffer batches after the timed loop (PCIe included): 1 warmup + 2 timed
+RING_BATCHES = 32                 # distinct pre-generated batches in HBM; longer runs go round them in new virtual time
+E2E_BATCHES = 6                  # host-buffer batches after the timed loop (PCIe included): 1 warmup + 2 timed
                                   # through pageable buffers, then the same through registered ones
 
 
@@ -42,13 +50,24 @@ def parse():
     ap.add_argument("--batch", type=int, default=PER_RANK_BATCH, help="requests per rank per step (avg)")
     ap.add_argument("--rules", type=int, default=N_RULES)
     ap.add_argument("--cpu-sample", type=int, default=1 << 25, help="oracle replay sample (requests)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (PCIe-inclusive) batches")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the first two timed batches")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the CPU baseline (with the host router and wire "
+                         "decoder timings), the host-buffer (PCIe-inclusive) batches and the oracle check of the "
+                         "first two timed batches (--config lines: the CPU baseline and its parity sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's results as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of the batch)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-buffer (PCIe-inclusive) batches")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the oracle check of the first two timed batches")
     ap.add_argument("--config", default="c3", choices=["c1", "c2", "c3", "c4", "c4args", "c4full", "c5a", "c5b"],
                     help="BASELINE.json configuration (SURVEY.md 8(d)); c3 = the headline, the others through "
                          "bench_local.py (c2 / c4 / c4full / c5b shard by resource over --gpus N)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_e2e = args.no_parity = True
+    return args
 
 
 def launch_ranks(args):
@@ -125,7 +144,7 @@ def main():
     fid_all, cnt_all = tr.rules()
     mine = shard_of(fid_all, n_gpus) == rank
 
-    # ---- pre-generate warmup+steps batches in HBM (untimed), plus the end-to-end batches that follow
+    # ---- pre-generate the warmup+steps batches' requests in HBM (untimed), plus the end-to-end batches that follow
     # the timed ones in virtual time (host buffers through sga_request_tokens, after the timed loop).
     # The timed entry takes the packed 12-byte records (sga_token_request, SURVEY.md 8(d) E_in);
     # SGA_BENCH_UNPACKED=1 times the four-array entry instead (A/B).
@@ -133,24 +152,56 @@ def main():
     n_e2e = 0 if args.no_e2e else E2E_BATCHES
     nb = args.warmup + args.steps
     nb_all = nb + n_e2e
+    # HBM stays bounded for any --steps: at most RING_BATCHES distinct batches are generated (about 0.6 GB each
+    # with its packed records and result buffer); batch b beyond them is batch b mod RING_BATCHES again at its own,
+    # later virtual time (the requests carry offsets from the batch's base time, as bench_local.py's steps do).
+    # Up to RING_BATCHES warmup + timed steps every batch is distinct, as before.
     gen = DeviceClusterGen(dev, n_rules=args.rules, lam=lam, n_shards=n_gpus, shard=rank)
-    batches, packed = [], []
-    touched = []
+    n_ring = max(1, min(nb, RING_BATCHES))
+    gen_at = [b for b in range(n_ring)] + [b for b in range(nb, nb_all)]
+    generated, packed_ring, touched_ring = {}, [], []
     max_n = 0
-    for b in range(nb_all):
+    for b in gen_at:
         f, a, p, t, ts_base, n, nt = gen.batch(b * glob_batch, glob_batch, touched=True)
-        touched.append(nt)
-        batches.append((f, a, p, t, ts_base, n))
-        packed.append(pack_requests(f, a, p, t) if b < nb and not unpacked else None)
+        generated[b] = (f, a, p, t, ts_base, n)
+        if b < nb:
+            touched_ring.append(nt)
+            packed_ring.append(pack_requests(f, a, p, t) if not unpacked else None)
         max_n = max(max_n, n)
     gen.tmp = None
+
+    class _PerBatch:
+        """batch index -> its value (list-like, read only)"""
+
+        def __init__(self, fn):
+            self.fn = fn
+
+        def __getitem__(self, b):
+            if isinstance(b, slice):
+                return [self.fn(k) for k in range(*b.indices(nb_all))]
+            return self.fn(b if b >= 0 else nb_all + b)
+
+    def batch_at(b):
+        if b >= nb:
+            return generated[b]
+        f, a, p, t, _, n = generated[b % n_ring]
+        return f, a, p, t, gen.ts_base(b * glob_batch), n
+
+    batches = _PerBatch(batch_at)
+    packed = _PerBatch(lambda b: packed_ring[b % n_ring] if b < nb else None)
+    touched = _PerBatch(lambda b: touched_ring[b % n_ring])
 
     eng = cluster.Engine(device=local, max_batch=max_n + 1024, max_rules=max(1 << 16, int(mine.sum()) + 1))
     cluster.ClusterFlowRuleManager(eng).load_rule_arrays("default", fid_all[mine], cnt_all[mine])
     L = _lib.load()
     estream = L.sga_engine_stream(eng.handle)
-    # every batch its own result buffer (the first two timed batches are checked against the oracle afterwards)
-    outs = [torch.empty(max(batches[b][5], 1), dtype=torch.int64, device=dev) for b in range(nb)]
+    # a result buffer per ring batch; the first two timed batches keep buffers of their own when they are checked
+    # against the oracle afterwards (a later step would otherwise write over them)
+    out_ring = [torch.empty(max(generated[b][5], 1), dtype=torch.int64, device=dev) for b in range(n_ring)]
+    out_kept = {}
+    if not args.no_parity and nb > n_ring:
+        out_kept = {b: torch.empty_like(out_ring[b % n_ring]) for b in range(args.warmup, min(args.warmup + 2, nb))}
+    outs = _PerBatch(lambda b: out_kept.get(b, out_ring[b % n_ring]))
 
     # HIP events on the engine stream: around the whole timed region and around every batch
     hip = C.CDLL("libamdhip64.so.7")
@@ -281,6 +332,9 @@ def main():
         else:
             coll_world, flows_gathered = 1, int(cnt_rows[0].item())
 
+    if args.dump_outputs:
+        dump_c3(args.dump_outputs, outs[nb - 1][: batches[nb - 1][5]], rank)
+
     e2e = run_e2e(L, eng, batches[nb:], dev) if n_e2e else None
 
     wall = t_end - t_start
@@ -347,7 +401,7 @@ def main():
             "data": "synthetic C3 trace (Zipf(1.1) flowIds, 1% prioritized, acquire 1), generated on GPU",
             "config": {"workload": "C3 cluster token server: DefaultTokenService.requestToken batches, "
                                    "1M cluster FlowRules (GLOBAL, count U{10..10000}, 10x100ms), sharded by flowId",
-                       "rules": args.rules, "requests_per_step_per_gpu": args.batch,
+                       "rules": args.rules, "requests_per_step_per_gpu": args.batch, "distinct_batches": n_ring,
                        "global_requests_per_step": args.batch * n_gpus, "lambda_per_virtual_s": lam,
                        "parallelism": f"shard{n_gpus}"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -381,6 +435,17 @@ def main():
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_c3(out_dir, result, rank):
+    """--dump-outputs: the TokenResults of the last timed batch as DefaultTokenService.request_tokens returns
+    them (status, remaining, wait_in_ms), decoded from the 8-byte records the timed entry wrote."""
+    from bench_local import dump_outputs
+    r = result.cpu().numpy().view(np.uint64)
+    dump_outputs(out_dir, rank, {
+        "status": ((r >> np.uint64(48)) & np.uint64(0xFF)).astype(np.int8),
+        "remaining": (r & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32),
+        "wait_in_ms": ((r >> np.uint64(32)) & np.uint64(0xFFFF)).astype(np.uint16).view(np.int16)})
 
 
 def check_parity(batches, outs, first, count, rule_fid, rule_cnt):

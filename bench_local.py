@@ -16,8 +16,8 @@ step shifts the batch's clock past the previous one, so each step is new virtual
 value = entries (C5a: descriptors) decided per second of wall time over the K timed steps.
 roofline.achieved = the algorithmic bytes of SURVEY.md 8(d) (N*(E_in+E_out) + per batch, per touched
 key, 2*S_k) / the GPU time of the steps (torch events on the one stream every call runs on).
-cpu_baseline = the C oracle (oracle/, test infrastructure) replaying a bounded sample of the same
-batch on one host thread."""
+cpu_baseline (bench.py --full only) = the C oracle (oracle/, test infrastructure) replaying a bounded
+sample of the same batch on one host thread."""
 import json
 import os
 import time
@@ -36,6 +36,29 @@ S_PARAM, S_PARAM_THROTTLE, S_BREAKER = 24, 16, 32
 
 
 SHARD = (0, 1)  # (rank, G) of this process (run_local sets it before building the configuration)
+
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: elements kept of each output array
+DUMP_SEED = 0x44554D50
+
+
+def dump_outputs(out_dir, rank, arrays, index="sample_index"):
+    """bench.py --dump-outputs: `arrays` (name -> host array, all of one length n, element i = event i of the last
+    timed step) as out_dir/<name>.npy in float64 (exact for every integer type written here).  Above DUMP_SAMPLE
+    elements a fixed sample is kept: the sorted distinct indices of DUMP_SAMPLE draws from a generator seeded with
+    DUMP_SEED, the same for every array and every run of the same n, stored beside them as <index>.npy.
+    Ranks above 0 write <name>.rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    idx = np.arange(n, dtype=np.int64)
+    if n > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+    sfx = f".rank{rank}" if rank else ""
+    for name, a in {**arrays, index: idx}.items():
+        a = np.asarray(a)
+        if name != index:
+            assert len(a) == n, f"dump_outputs: {name} has {len(a)} elements, expected {n}"
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a.astype(np.float64))
 
 
 def own_resources(n_res):
@@ -492,7 +515,7 @@ def run_local(args, cfg_name):
 
     for k in range(args.warmup):
         step(k)
-        if k == 0:
+        if k == 0 and not args.no_cpu:  # only the CPU leg's parity check reads them
             keep_first()
     torch.cuda.synchronize(dev)
     s.device_status()
@@ -514,6 +537,11 @@ def run_local(args, cfg_name):
         first = None
     gpu_s = ev0.elapsed_time(ev1) / 1e3
     d = dec.cpu().numpy()
+    if getattr(args, "dump_outputs", None):  # the last timed step: the entries' decisions and waits, the exits' decisions
+        outs = {"decision": d, "wait_ms": wait.cpu().numpy()}
+        if has_exit:
+            outs["exit_decision"] = x_dec.cpu().numpy()
+        dump_outputs(args.dump_outputs, rank, outs)
     n_ent_rank = b.n * args.steps
     n_ent = n_ent_rank
     if dist is not None:  # max of the ranks' times, sum of their entries
@@ -623,6 +651,10 @@ def run_rls(args):
     wall = time.perf_counter() - t0
     gpu_s = ev0.elapsed_time(ev1) / 1e3
     code = out["r"][0].cpu().numpy()
+    if getattr(args, "dump_outputs", None):  # the last timed step: code per request, status / remaining per descriptor
+        dump_outputs(args.dump_outputs, 0, {"code": code}, index="request_index")
+        dump_outputs(args.dump_outputs, 0, {"status": out["r"][1].cpu().numpy(), "remaining": out["r"][2].cpu().numpy()},
+                     index="descriptor_index")
     touched = len(np.unique(dfid))
     bytes_alg = (nd * (E_RLS_IN + E_RLS_OUT) + 2 * touched * S_RLS) * args.steps
     achieved = bytes_alg / gpu_s / 1e9

@@ -21,7 +21,7 @@ for rep in 1 2; do
   for envs in "$@"; do
     i=$((i+1))
     extra="--no-parity"; [ $rep = 1 ] && extra=""
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu --no-e2e $extra > $out/ab_${i}_$rep.json 2> $out/ab_${i}_$rep.err || { echo "FAIL [$envs]"; tail -5 $out/ab_${i}_$rep.err; exit 1; }
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu --no-e2e $extra > $out/ab_${i}_$rep.json 2> $out/ab_${i}_$rep.err || { echo "FAIL [$envs]"; tail -5 $out/ab_${i}_$rep.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$out/ab_${i}_$rep.json').read().strip().splitlines()[-1]); p=d.get('parity_sample') or {}; print('[$envs] ms %.4f gpu_ms %.4f mism %s' % (d['ms_per_step'], d['roofline']['gpu_ms_per_step'], p.get('mismatches')))"
   done
 done

@@ -9,7 +9,7 @@ mkdir -p $out
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg timeout -k 10 200 rocprofv3 --kernel-trace --stats -d /tmp/abt_$i -o run --output-format csv -- python3 bench.py --no-cpu --steps 10 --warmup 3 > $out/run_$i.json 2> $out/run_$i.err || { echo "FAILED: $cfg"; tail -5 $out/run_$i.err; exit 1; }
+  env $cfg timeout -k 10 200 rocprofv3 --kernel-trace --stats -d /tmp/abt_$i -o run --output-format csv -- python3 bench.py --full --no-cpu --steps 10 --warmup 3 > $out/run_$i.json 2> $out/run_$i.err || { echo "FAILED: $cfg"; tail -5 $out/run_$i.err; exit 1; }
   f=$(find /tmp/abt_$i -name '*kernel_trace.csv' | head -1)
   cp $f $out/trace_$i.csv
   python3 -c "import json,sys; d=json.loads(open('$out/run_$i.json').read().strip().splitlines()[-1]); print('== %-30s value=%.4g gpu_ms=%.3f frac=%.4f' % (sys.argv[1], d['value'], d['roofline']['gpu_ms_per_step'], d['roofline']['frac']))" "$cfg"

@@ -3,7 +3,7 @@
 # (FETCH_SIZE and WRITE_SIZE in passes of their own, kernel trace only, as MI355X_MICROARCH.md prescribes):
 # calibration (tools/calib/pmccal), then per configuration two counter passes and a kernel trace of the bench
 # line, summarised by tools/pmc_summary.py into gpurun_out/<tag>/traffic_<cfg>.json.
-# c3: bench.py --steps 5 --warmup 1 --no-cpu --no-e2e; c2/c4/c5b: bench.py --config <cfg> --steps 2 --warmup 1 --no-cpu.
+# c3: bench.py --full --steps 5 --warmup 1 --no-cpu --no-e2e; c2/c4/c5b: bench.py --config <cfg> --steps 2 --warmup 1 --no-cpu.
 set -o pipefail
 export TMPDIR=/tmp
 tag=${1:-r04p}; shift
@@ -22,7 +22,7 @@ python3 tools/pmc_cal.py $out/cal --json $out/cal/cal.json || exit 1
 for cfg in $cfgs; do
   d=$out/$cfg
   mkdir -p $d
-  if [ "$cfg" = "c3" ]; then args="--steps 5 --warmup 1 --no-cpu --no-e2e"; extra="";
+  if [ "$cfg" = "c3" ]; then args="--full --steps 5 --warmup 1 --no-cpu --no-e2e"; extra="";
   else args="--config $cfg --steps 2 --warmup 1 --no-cpu"; extra="--all-random"; fi
   i=0
   for set in FETCH_SIZE WRITE_SIZE; do

@@ -9,7 +9,7 @@ mkdir -p $out
 i=0
 for set in "$@"; do
   i=$((i+1))
-  timeout -s KILL 90 rocprofv3 --pmc $set --kernel-include-regex "$rx" -d /tmp/pmck_${tag}_$i -o run --output-format csv -- python3 bench.py --no-cpu --steps 3 --warmup 2 > $out/bench_$i.out 2>&1 || exit $?
+  timeout -s KILL 90 rocprofv3 --pmc $set --kernel-include-regex "$rx" -d /tmp/pmck_${tag}_$i -o run --output-format csv -- python3 bench.py --full --no-cpu --steps 3 --warmup 2 > $out/bench_$i.out 2>&1 || exit $?
   find /tmp/pmck_${tag}_$i -name "*counter_collection.csv" -exec cp {} $out/counters_$i.csv \;
 done
 python3 tools/pmc_summary.py $out > $out/summary.txt

@@ -16,7 +16,7 @@ print(sys.argv[2], "n_gpus", d["n_gpus"], "ms %.3f" % d["ms_per_step"], "value %
       "group_size", m.get("group_size"), "parity", json.dumps(d.get("parity_sample"))[:160])
 PY
 }
-run c3_gpus2 "SGA_BENCH_ONE_DEVICE=1" --gpus 2 --no-cpu --no-e2e
-run c2_gpus2 "SGA_BENCH_ONE_DEVICE=1" --config c2 --gpus 2
-run c3_gpus1 "SGA_NONE=0" --no-cpu --no-e2e
+run c3_gpus2 "SGA_BENCH_ONE_DEVICE=1" --full --gpus 2 --no-cpu --no-e2e
+run c2_gpus2 "SGA_BENCH_ONE_DEVICE=1" --full --config c2 --gpus 2
+run c3_gpus1 "SGA_NONE=0" --full --no-cpu --no-e2e
 run c3_nometric "SGA_BENCH_METRIC_EVERY=100000" --no-cpu --no-e2e --no-parity
