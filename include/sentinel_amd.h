@@ -381,7 +381,8 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
 /* ---------------------------------------------------------------------------
  * Local path: resources are dense ids 0..n_resources-1 (the host keeps the
  * name table, like CtSph's chain map keys).  One ClusterNode per resource
- * (single default context, limitApp "default", strategy DIRECT).
+ * (single default context, limitApp "default"; strategy DIRECT or RELATE:
+ * FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116).
  * ------------------------------------------------------------------------- */
 
 /* Coalescing queue of single local events (SphU.entry / Entry.exit from many application threads, one
@@ -457,7 +458,11 @@ int sga_event_post(sga_engine *e, uint8_t kind, uint32_t resource, int64_t ts, i
 /* resource id of Constants.ENTRY_NODE ("__total_inbound_traffic__") in sga_query_node and metric rows */
 #define SGA_ENTRY_NODE 0xFFFFFFFFu
 
-/* FlowRule, CORE/slots/block/flow/FlowRule.java:52-95 (limitApp default, strategy DIRECT) */
+/* resource id that names no resource (a RELATE rule's refResource outside the engine; "no group") */
+#define SGA_REF_NONE 0xFFFFFFFFu
+
+/* FlowRule, CORE/slots/block/flow/FlowRule.java:52-95 (limitApp default; strategy DIRECT or RELATE, the node
+ * the rule's controller reads chosen as in FlowRuleChecker.java:96-116) */
 typedef struct sga_flow_rule {
     uint32_t resource;
     int32_t grade;                 /* FLOW_GRADE_THREAD 0 / QPS 1 */
@@ -465,7 +470,7 @@ typedef struct sga_flow_rule {
     int32_t control_behavior;      /* 0 default, 1 warm up, 2 rate limiter, 3 warm up + rate limiter */
     int32_t warm_up_period_sec;    /* default 10 */
     int32_t max_queueing_time_ms;  /* default 500 */
-    int32_t strategy;              /* STRATEGY_DIRECT 0 only */
+    int32_t strategy;              /* STRATEGY_DIRECT 0 or STRATEGY_RELATE 1 (CHAIN 2 and negatives: invalid rule) */
     /* FlowRule.clusterMode (FlowRuleChecker.passClusterCheck, FlowRuleChecker.java:168-230): the
      * rule asks the token service; with the embedded server (sga_set_cluster_server) that is this
      * engine's cluster rules (sga_load_cluster_flow_rules, keyed by flowId) */
@@ -475,7 +480,13 @@ typedef struct sga_flow_rule {
     int32_t cluster_sample_count;  /* ClusterFlowConfig.sampleCount / windowIntervalMs / strategy: */
     int32_t cluster_window_ms;     /*   validity only (FlowRuleUtil.checkClusterField) */
     int32_t cluster_strategy;
-    int32_t reserved;
+    /* RELATE: refResource as a dense resource id.  The rule's controller reads that resource's ClusterNode
+     * (passQps / curThreadNum / occupy), the entered resource's own node still counts the pass or block.  The
+     * rule passes untouched until the referenced resource has been entered once (its ClusterNode is null before:
+     * FlowRuleChecker.java:86-89); an id >= n_resources (SGA_REF_NONE) names a resource that never is, so the
+     * rule is valid, counted as loaded and never blocks.  A blank refResource is invalid (FlowRuleUtil.java:246-251):
+     * the caller passes strategy -1.  Ignored with DIRECT. */
+    uint32_t ref_resource;
 } sga_flow_rule;
 
 /* ParamFlowRule, PF/slots/block/flow/param/ParamFlowRule.java:45-83 */
@@ -532,6 +543,11 @@ typedef struct sga_node_view {
 
 int sga_flow_set_resources(sga_engine *e, uint32_t n_resources);
 int sga_load_flow_rules(sga_engine *e, const sga_flow_rule *rules, size_t n);
+/* Resources linked by RELATE rules (a rule's resource and its refResource, transitively) form a group whose
+ * events are decided in arrival order by one lane; everything else stays parallel per resource.  *leader = the
+ * smallest resource id of `resource`'s group, or SGA_REF_NONE when no loaded RELATE rule couples it.  A
+ * multi-GPU deployment must route a group's resources to one engine. */
+int sga_flow_group_of(sga_engine *e, uint32_t resource, uint32_t *leader);
 /* ClusterStateManager for the local path's cluster-mode FlowRules (FlowRuleChecker.pickClusterService):
  * 0 = neither client nor server (cluster-mode rules fall back: fallbackToLocalOrPass), 1 = embedded
  * token server -- the rule's flowId is decided by this engine's cluster path in event order

@@ -143,13 +143,19 @@ public final class GpuRuleSync {
                 int base = b.position();
                 b.putInt(GpuStatisticSlot.resourceId(r.getResource())).putInt(r.getGrade()).putDouble(r.getCount());
                 b.putInt(r.getControlBehavior()).putInt(r.getWarmUpPeriodSec()).putInt(r.getMaxQueueingTimeMs());
-                b.putInt(r.getStrategy());
+                // the engine serves limitApp "default" with strategy DIRECT (0) or RELATE (1, a non-blank
+                // refResource: FlowRuleUtil.checkStrategyField); anything else is an invalid rule to it (-1)
+                String ref = r.getRefResource();
+                boolean relate = r.getStrategy() == 1 && ref != null && !ref.trim().isEmpty();
+                boolean served = "default".equals(r.getLimitApp()) && (r.getStrategy() == 0 || relate);
+                b.putInt(served ? r.getStrategy() : -1);
                 boolean cm = r.isClusterMode() && r.getClusterConfig() != null;
                 b.putInt(cm ? 1 : 0).putInt(cm && r.getClusterConfig().isFallbackToLocalWhenFail() ? 1 : 0);
                 b.putLong(cm && r.getClusterConfig().getFlowId() != null ? r.getClusterConfig().getFlowId() : 0L);
                 b.putInt(cm ? r.getClusterConfig().getSampleCount() : 0);
                 b.putInt(cm ? r.getClusterConfig().getWindowIntervalMs() : 0);
-                b.putInt(cm ? r.getClusterConfig().getStrategy() : 0).putInt(0);
+                b.putInt(cm ? r.getClusterConfig().getStrategy() : 0);
+                b.putInt(served && relate ? GpuStatisticSlot.resourceId(ref) : 0);  // ref_resource
                 b.position(base + 64);
             }
             b.flip();

@@ -58,7 +58,10 @@ class SgaFlowRule(C.Structure):
                 ("max_queueing_time_ms", C.c_int32), ("strategy", C.c_int32),
                 ("cluster_mode", C.c_int32), ("cluster_fallback", C.c_int32), ("cluster_flow_id", C.c_int64),
                 ("cluster_sample_count", C.c_int32), ("cluster_window_ms", C.c_int32),
-                ("cluster_strategy", C.c_int32), ("reserved", C.c_int32)]
+                ("cluster_strategy", C.c_int32), ("ref_resource", C.c_uint32)]
+
+
+SGA_REF_NONE = 0xFFFFFFFF  # a RELATE rule's refResource outside the engine; sga_flow_group_of: ungrouped
 
 
 class SgaParamRule(C.Structure):
@@ -165,6 +168,7 @@ SIGNATURES = {
     "sga_load_system_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "sga_set_system_status": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "sga_load_flow_rules": (C.c_int, [C.c_void_p, C.POINTER(SgaFlowRule), C.c_size_t]),
+    "sga_flow_group_of": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sga_set_cluster_server": (C.c_int, [C.c_void_p, C.c_int32]),
     "sga_load_param_rules": (C.c_int, [C.c_void_p, C.POINTER(SgaParamRule), C.c_size_t]),
     "sga_load_degrade_rules": (C.c_int, [C.c_void_p, C.POINTER(SgaDegradeRule), C.c_size_t]),

@@ -2379,6 +2379,10 @@ int sga_load_flow_rules(sga_engine *e, const sga_flow_rule *rules, size_t n) {
     });
 }
 
+int sga_flow_group_of(sga_engine *e, uint32_t resource, uint32_t *leader) {
+    return guarded(e, [&](Engine &g) { return g.flow.group_of(resource, leader); });
+}
+
 int sga_load_param_rules(sga_engine *e, const sga_param_rule *rules, size_t n) {
     if (n && !rules) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {

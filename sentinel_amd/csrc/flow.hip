@@ -43,6 +43,9 @@ enum : int8_t { D_PASS = 0, D_BLOCK_FLOW = 1, D_BLOCK_PARAM = 2, D_BLOCK_DEGRADE
 enum : uint32_t { F_SPECIAL = 1u << 31, F_EXIT = 1u << 30, F_ERROR = 1u << 29, F_PARAM = 1u << 28,
                   F_IDX = (1u << 28) - 1 };
 constexpr uint32_t kHeavyEvents = 1024;  // per batch: replayed by k_lheavy instead of one k_lflows lane
+// a RELATE group with this many events in a chunk is replayed by a wave of k_lgroup instead of its k_lflows
+// lane (below that the lane's neighbours wait less for it than a second kernel's staging costs)
+constexpr uint32_t kGroupEvents = 128;
 #ifndef SGA_WAVE_EVENTS
 #define SGA_WAVE_EVENTS 128
 #endif
@@ -940,7 +943,17 @@ __device__ int8_t chain_entry(const Ctx &c, uint32_t r, const ResMem &m, int64_t
             }
             if (!fr.cfallback) continue;  // fallbackToLocalOrPass: the rule is not activated
         }
-        const int8_t d = rater_can_pass(c, fr, node, t, acquire, prio, &w);
+        // selectNodeByRequesterAndStrategy (FlowRuleChecker.java:96-116), limitApp "default": DIRECT reads the
+        // resource's own ClusterNode, RELATE refResource's -- null (the rule passes, nothing touched, :86-89)
+        // until that resource has been entered.  Only the rater sees it: StatisticSlot counts on the own node.
+        int64_t *sel = node;
+        if (fr.rel) {
+            const uint32_t ref = fr.rel - 1u;
+            if (ref >= c.st.nres) continue;
+            sel = c.st.node + (size_t)ref * kNodeWords;
+            if (!sel[kNodeEntered]) continue;
+        }
+        const int8_t d = rater_can_pass(c, fr, sel, t, acquire, prio, &w);
         if (d == D_BLOCK_FLOW) {
             node_add(c, node, t, MB_BLOCK, acquire);
             *wait_ms = (int64_t)k;
@@ -1166,6 +1179,7 @@ __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *
             if (in) entry_node_after_exit(c, t, rt_in[i], a, (fl & SGA_EV_ERROR) != 0);
             continue;
         }
+        st.node[(size_t)r * kNodeWords + kNodeEntered] = 1;  // ClusterBuilderSlot.entry: ahead of every check
         if (kind[i] == SGA_KIND_BLOCKED) {  // StatisticSlot's BlockException branch for a block thrown outside the engine
             blocked_event(c, r, t, a);
             if (in) node_add(c, entry_node(c), t, MB_BLOCK, a);
@@ -1370,7 +1384,11 @@ __global__ __launch_bounds__(kT) void k_lclassify(FlowState st, FlowScratch sc, 
         pay[i] = Payload{i, 0, 0, 0};
         return;
     }
-    keys[i] = r;
+    // A RELATE group's events (FlowEngine::load_flow_rules) sort under the group's leader and replay in arrival
+    // order, each with its original kind and arguments (F_SPECIAL); the replay marks their resources entered
+    // in that order (an ungrouped resource's mark: k_lflows, once per flow).
+    const uint32_t grp = st.has_groups ? st.res[r].group : kNoGroup;
+    keys[i] = grp != kNoGroup ? grp : r;
     const uint32_t off = ts_off[i];
     const int64_t t = ts_base + (int64_t)off;
     // the parameter the parallel kernels read (ev_param): the event's own, or its argument vector's one value
@@ -1381,12 +1399,12 @@ __global__ __launch_bounds__(kT) void k_lclassify(FlowState st, FlowScratch sc, 
     } else if (hp && (fl & SGA_EV_PARAM_LIST)) {
         kept = true;
     }
-    const bool spec = kept || kd >= SGA_KIND_BLOCKED;
+    const bool spec = kept || kd >= SGA_KIND_BLOCKED || grp != kNoGroup;
     // the resource's level this chunk (res_special = epoch << 2 | level, the highest wins): 1 -- kind 2 / 3 events
     // only, which the per-value segments of a parameter-only resource also take (a revoke is an exit there
     // that takes its pass back); 2 -- arguments kept whole: the per-resource replay
     const uint32_t lvl = kept ? 2u : (spec ? 1u : 0u);
-    if (spec && sc.res_special) {
+    if (spec && grp == kNoGroup && sc.res_special) {
         const uint32_t mark = (sc.epoch << 2) | lvl;
         if (sc.res_special[r] < mark) atomicMax(&sc.res_special[r], mark);
     }
@@ -1778,6 +1796,26 @@ __device__ __forceinline__ void replay_event(const Ctx &c, const FlowScratch &sc
     }
 }
 
+// One event of a RELATE group's replay (k_lflows inline, k_lgroup, k_lsmall): ClusterBuilderSlot.entry creates
+// the resource's ClusterNode ahead of every check (kind 0 / 2 / 3), in arrival order -- a RELATE rule of
+// another member passes until then (chain_entry); then the slot chain.  q carries F_SPECIAL.
+__device__ __forceinline__ void group_event(const Ctx &c, const FlowScratch &sc, uint32_t res, const Payload &q,
+                                            int64_t ts_base, const int64_t *__restrict__ rt_in, int8_t *decision,
+                                            int32_t *wait_ms) {
+    if (sc.in_kind[q.idx & F_IDX] != 1) c.st.node[(size_t)res * kNodeWords + kNodeEntered] = 1;
+    replay_event<true>(c, sc, res, q, ts_base, rt_in, sc.in_param, decision, wait_ms);
+}
+
+// A short group's events on its k_lflows lane (a call, like lane_run: the kernel's other paths keep their registers)
+__device__ __noinline__ void group_inline(const Ctx &c, const FlowScratch &sc, const Payload *__restrict__ pay,
+                                          uint32_t j0, uint32_t nev, int64_t ts_base,
+                                          const int64_t *__restrict__ rt_in, int8_t *decision, int32_t *wait_ms) {
+    for (uint32_t j = j0; j < j0 + nev; ++j) {
+        const Payload q = pay[j];
+        group_event(c, sc, sc.in_resource[q.idx & F_IDX], q, ts_base, rt_in, decision, wait_ms);
+    }
+}
+
 // Small batches (the coalescing event queue's rounds, a single SphU.entry): one workgroup.  The first event of
 // each resource in the batch leads: its lane replays the resource's events in arrival order with the whole slot
 // chain (replay_event, as lane_run does for a resource with F_SPECIAL events), the resources side by side; then
@@ -1794,25 +1832,29 @@ __global__ __launch_bounds__(kLSmall) void k_lsmall(FlowState st, int64_t max_rt
                                                     const int32_t *__restrict__ acquire,
                                                     const int64_t *__restrict__ rt_in, uint32_t n, int8_t *decision,
                                                     int32_t *wait_ms, uint32_t *ovf_out, int zero_ovf) {
-    __shared__ uint32_t sres[FlowEngine::kSmallEvents];
+    // skey: what replays together in arrival order -- the resource, or its RELATE group's leader (a member id)
+    __shared__ uint32_t sres[FlowEngine::kSmallEvents], skey[FlowEngine::kSmallEvents];
     const uint32_t i = threadIdx.x;
     const Ctx c{st, max_rt};
     if (zero_ovf && i == 0) *st.overflow = 0;  // no lru_prepare ahead of this kernel: the batch's overflow word
     for (uint32_t k = i; k < n; k += kLSmall) {
-        sres[k] = resource[k];
+        const uint32_t r = resource[k];
+        const uint32_t grp = (st.has_groups && r < st.nres) ? st.res[r].group : kNoGroup;
+        sres[k] = r;
+        skey[k] = grp != kNoGroup ? grp : r;
         decision[k] = D_PASS;
         wait_ms[k] = 0;
     }
     __syncthreads();
-    for (uint32_t k = i; k < n; k += kLSmall) {  // each resource's first event leads: its lane replays them in order
-        const uint32_t r = sres[k];
-        bool lead = r < st.nres;
-        for (uint32_t j = 0; j < k && lead; ++j) lead = sres[j] != r;
+    for (uint32_t k = i; k < n; k += kLSmall) {  // each key's first event leads: its lane replays them in order
+        const uint32_t key = skey[k];
+        bool lead = sres[k] < st.nres;
+        for (uint32_t j = 0; j < k && lead; ++j) lead = skey[j] != key;
         if (lead)
             for (uint32_t j = k; j < n; ++j) {
-                if (sres[j] != r) continue;
+                if (skey[j] != key) continue;
                 const Payload q{j | F_SPECIAL, ts_off[j], (uint32_t)acquire[j] & 0x7FFFFFFFu, 0u};
-                replay_event<true>(c, fs, r, q, ts_base, rt_in, fs.in_param, decision, wait_ms);
+                group_event(c, fs, sres[j], q, ts_base, rt_in, decision, wait_ms);
             }
     }
     __syncthreads();
@@ -2186,6 +2228,30 @@ __global__ __launch_bounds__(kT) void k_lflows(FlowState st, int64_t max_rt, Flo
             // in arrival order on this lane (k_llru in LRU mode); the other resources keep every parallel form
             const uint32_t rs = sc.res_special ? sc.res_special[res] : 0u;
             const uint32_t special = (rs >> 2) == sc.epoch ? (rs & 3u) : 0u;  // level (k_lclassify)
+            // a RELATE group (the key is its leader): its members' events in arrival order, each against its own
+            // resource -- here when short, by a wave of k_lgroup otherwise; no per-resource form applies
+            if (st.has_groups && st.res[res].group != kNoGroup) {
+                if (nev >= kGroupEvents) {
+                    sc.group[wave_append(&sc.counters[15])] = fl;
+                    continue;
+                }
+                group_inline(c, sc, pay, sc.run_start[r0], nev, ts_base, rt_in, decision, wait_ms);
+                for (uint32_t r = r0; r < r1; ++r) sc.run_mode[r] = RUN_DONE;
+                continue;
+            }
+            // ClusterBuilderSlot.entry ran for the resource (kNodeEntered): the flow holds an entry or a kind-2
+            // event (run_nent counts both), or -- only a flow with F_SPECIAL events can -- a revoke among its
+            // exits.  Nobody reads an ungrouped resource's mark within the chunk -- a rule that names it groups
+            // it -- so one plain store per flow, not one per event (the hot resources' events would queue up on
+            // one line)
+            {
+                bool ent = false;
+                for (uint32_t r = r0; r < r1 && !ent; ++r) ent = sc.run_nent[r] != 0;
+                if (!ent && special)
+                    for (uint32_t j = sc.run_start[r0], je = j + nev; j < je && !ent; ++j)
+                        ent = sc.in_kind[pay[j].idx & F_IDX] == SGA_KIND_REVOKE;
+                if (ent) st.node[(size_t)res * kNodeWords + kNodeEntered] = 1;
+            }
             if (st.lru_res && st.lru_res[res]) {  // a CacheMap in LRU mode: arrival order, one lane (k_llru)
                 // parameter-only: the chunked replay (k_llru_ps, SGA_LRU_PS=0 turns it off: an A/B knob)
                 const bool ps = !special && st.lru_ps && lru_ps_take(st, sc, pay, res, r0, r1);
@@ -3411,6 +3477,43 @@ __global__ __launch_bounds__(64) void k_lheavy(FlowState st, int64_t max_rt, Flo
         if (lc)
             for (uint32_t k = threadIdx.x; k < R.n_cbs; k += 64) g.cbs[k] = lcbs[k];
         __syncthreads();
+    }
+}
+
+// RELATE groups with kGroupEvents events or more in the chunk (k_lflows lists them): one wave each.  The
+// group's events -- every member resource's, sorted under the leader, in arrival order -- are staged into
+// LDS tile by tile (coalesced loads of the payloads, a gather of the events' own resources), and lane 0
+// replays each tile in order against global state: a member's RELATE rule reads another member's node as
+// the events before it left it.  Exact and sequential per group; groups run side by side.
+constexpr int kGroupTile = 256;
+__global__ __launch_bounds__(64) void k_lgroup(FlowState st, int64_t max_rt, FlowScratch sc,
+                                               const Payload *__restrict__ pay, int64_t ts_base,
+                                               const int64_t *__restrict__ rt_in, int8_t *decision,
+                                               int32_t *wait_ms) {
+    if (!gate_is(st.gate, kGateSeq | kGateBad, 0)) return;
+    __shared__ Payload spay[kGroupTile];
+    __shared__ uint32_t sres[kGroupTile];
+    const Ctx c{st, max_rt};
+    const uint32_t ng = sc.counters[15], nflows = sc.counters[2], nruns = sc.counters[1];
+    for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) {
+        const uint32_t fl = sc.group[g];
+        const uint32_t r0 = sc.flow_first_run[fl];
+        const uint32_t r1 = fl + 1 < nflows ? sc.flow_first_run[fl + 1] : nruns;
+        const uint32_t je = sc.run_end[r1 - 1];
+        for (uint32_t base = sc.run_start[r0]; base < je; base += kGroupTile) {
+            const uint32_t m = min((uint32_t)kGroupTile, je - base);
+            for (uint32_t k = threadIdx.x; k < m; k += 64) {
+                const Payload q = pay[base + k];
+                spay[k] = q;
+                sres[k] = sc.in_resource[q.idx & F_IDX];
+            }
+            __syncthreads();
+            if (threadIdx.x == 0)
+                for (uint32_t k = 0; k < m; ++k)
+                    group_event(c, sc, sres[k], spay[k], ts_base, rt_in, decision, wait_ms);
+            __syncthreads();
+        }
+        for (uint32_t r = r0 + threadIdx.x; r < r1; r += 64) sc.run_mode[r] = RUN_DONE;
     }
 }
 
@@ -5514,6 +5617,8 @@ __global__ void k_init_nodes(int64_t *node, uint32_t n, int64_t max_rt) {
     }
     p[kNodeThreads] = 0;
     p[kNodeLastFetch] = -1;
+    p[kNodeEntered] = 0;
+    p[kNodeEntered + 1] = 0;  // spare
 }
 
 // StatisticNode.metrics() (CORE/node/StatisticNode.java:120-157) over ArrayMetric.details()
@@ -5640,6 +5745,7 @@ FlowState FlowEngine::state() const {
     s.pmask = tab_slots(d_ptab) ? (uint32_t)(tab_slots(d_ptab) - 1) : 0;
     s.tmask = tab_slots(d_ttab) ? (uint32_t)(tab_slots(d_ttab) - 1) : 0;
     s.nres = nres;
+    s.has_groups = has_groups ? 1u : 0u;
     s.overflow = d_overflow.p;
     s.cst = cluster_st;
     s.cluster_on = cluster_on;
@@ -5902,10 +6008,14 @@ int FlowEngine::set_resources(uint32_t n) {
 void FlowEngine::upload_res() {
     for (uint32_t r = 0; r < nres; ++r) {
         ResDev &R = h_res[r];
-        R.fast &= 2u;  // bit1 (a thread-count map exists) is sticky
-        if (R.n_rules == 1 && R.n_prules == 0 && R.n_cbs == 0 && !(R.fast & 2u)) {
+        R.fast &= 2u;  // bit1 (a thread-count map exists) is sticky, for a grouped resource too: it is state, no
+                       // fast path (bits 0 and 2 stay clear for a group, and k_lflows tests for the group first)
+        R.group = r < h_group.size() ? h_group[r] : kNoGroup;
+        if (R.n_rules == 1 && R.n_prules == 0 && R.n_cbs == 0 && !(R.fast & 2u) && R.group == kNoGroup) {
             const FlowRuleDev &fr = h_rules[R.rule_off];
-            if (fr.cluster) {
+            if (fr.rel) {
+                // RELATE to a resource the engine does not have: the rule never applies (chain_entry skips it)
+            } else if (fr.cluster) {
                 // cluster-mode rule: every entry asks the token server (per-event replay)
             } else if (fr.grade == 1 && (fr.behavior == 0 || fr.behavior == 1)) R.fast = 1;
             else if (fr.grade == 1 && fr.behavior == 2) R.fast = 4;  // pacing only: k_lflows register loop
@@ -5924,7 +6034,9 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n) {
     for (size_t i = 0; i < n; ++i) {
         const sga_flow_rule &r = rules[i];
         if (r.resource >= nres) continue;
-        bool ok = r.count >= 0 && r.grade >= 0 && r.strategy >= 0 && r.control_behavior >= 0 && r.strategy == 0;
+        // FlowRuleUtil.isValidRule + checkStrategyField (:246-251): DIRECT, or RELATE (the binding layer turns a
+        // blank refResource into strategy -1); CHAIN and origin-specific limitApp are not served
+        bool ok = r.count >= 0 && r.grade >= 0 && r.control_behavior >= 0 && (r.strategy == 0 || r.strategy == 1);
         if (ok && r.cluster_mode) {  // FlowRuleUtil.checkClusterField / checkClusterConcurrentField (:197-240)
             ok = r.cluster_flow_id > 0 && r.cluster_sample_count > 0 && r.cluster_window_ms > 0 &&
                  r.cluster_window_ms % r.cluster_sample_count == 0 && (r.grade != 1 || r.cluster_strategy == 0);
@@ -5952,6 +6064,7 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n) {
         d.cfallback = r.cluster_fallback ? 1 : 0;
         d.cflow = r.cluster_flow_id;
         d.cslot = -1;
+        d.rel = r.strategy == 1 ? std::min(r.ref_resource, nres) + 1u : 0u;
         if (d.behavior == 1 || d.behavior == 3) {  // WarmUpController.construct, :83-106
             d.warning_token = j_d2i((double)r.warm_up_period_sec * r.count) / (cfg.cold_factor - 1);
             d.max_token = d.warning_token + j_d2i(2 * r.warm_up_period_sec * r.count / (1.0 + cfg.cold_factor));
@@ -5959,6 +6072,32 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n) {
         }
         per[r.resource].push_back(d);
         valid++;
+    }
+    // RELATE groups: the components of the (resource, refResource) pairs -- a resource whose only RELATE rule
+    // names itself is a component of one -- each led by its smallest member.  A group's events are decided in
+    // arrival order by one lane (k_lflows / k_lgroup / k_lsmall); everything else stays per resource.
+    {
+        std::vector<uint32_t> parent(nres);
+        std::vector<uint8_t> grouped(nres, 0);
+        for (uint32_t r = 0; r < nres; ++r) parent[r] = r;
+        auto find = [&](uint32_t x) {
+            while (parent[x] != x) x = parent[x] = parent[parent[x]];
+            return x;
+        };
+        for (uint32_t r = 0; r < nres; ++r)
+            for (const FlowRuleDev &d : per[r]) {
+                if (!d.rel || d.rel - 1u >= nres) continue;
+                const uint32_t a = find(r), b = find(d.rel - 1u);
+                parent[std::max(a, b)] = std::min(a, b);  // the smaller root stays: the leader
+                grouped[r] = grouped[d.rel - 1u] = 1;
+            }
+        h_group.assign(nres, kNoGroup);
+        has_groups = false;
+        for (uint32_t r = 0; r < nres; ++r)
+            if (grouped[r]) {
+                h_group[r] = find(r);
+                has_groups = true;
+            }
     }
     h_rules.clear();
     has_cluster_rules = false;
@@ -5977,6 +6116,12 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n) {
     upload_res();
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
     return valid;
+}
+
+int FlowEngine::group_of(uint32_t resource, uint32_t *leader) const {
+    if (!leader || resource >= nres) return SGA_EINVAL;
+    *leader = resource < h_group.size() ? h_group[resource] : kNoGroup;
+    return 0;
 }
 
 // ParamFlowRule.equals (ParamFlowRule.java:192-210) of a loaded rule -- whose paramIdx the slot may have
@@ -6463,7 +6608,8 @@ int FlowEngine::ensure_scratch() {
                        al(cap * 8) +  // ev_param
                        al(cap * sizeof(Payload)) +  // spay
                        4 * al((cap / kCbTileMin + 2) * 4) + al((cap / kCbTileMin + 2) * sizeof(CbAgg)) +  // cbt_*
-                       al((2 * (cap / kCbRound) + 16) * 4) + al((2 * (cap / kCbRound) + 16) * sizeof(CbTile)) + al(64);
+                       al((2 * (cap / kCbRound) + 16) * 4) + al((2 * (cap / kCbRound) + 16) * sizeof(CbTile)) + al(64) +
+                       al(cap * 4);  // group (last: the other arrays keep their places)
         d_scratch.alloc(bytes);
         char *p = (char *)d_scratch.p;
         auto take = [&](size_t b) {
@@ -6531,6 +6677,7 @@ int FlowEngine::ensure_scratch() {
             sc.cbt = (CbTile *)take(nt * sizeof(CbTile));
             sc.cbt_ctl = (uint32_t *)take(64);
         }
+        sc.group = (uint32_t *)take(cap * 4);
         sc.cap = cap;
         scratch_cap = cap;
         d_kind.alloc(cap);
@@ -6597,6 +6744,7 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
     fs.in_flags = dfl;
     fs.in_param = dpar;
     fs.pvals = dvals;
+    fs.in_resource = dres;
     hipLaunchKernelGGL(k_lsmall, dim3(1), dim3(kLSmall), 0, stream, state(), (int64_t)cfg.statistic_max_rt, fs, dres,
                        dts, lo, dacq, drt, m, (int8_t *)(d + o_dec), (int32_t *)(d + o_wait), (uint32_t *)(d + o_ovf),
                        maps ? 0 : 1);
@@ -6615,7 +6763,8 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
 // The chunk's view of the scratch for F_SPECIAL events: a new epoch marks their resources (res_special), the
 // original kind / flags / parameters / value lists are what the per-resource replay reads for them.
 FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
-                                        const uint64_t *d_param_in, const uint64_t *d_pvals) {
+                                        const uint64_t *d_param_in, const uint64_t *d_pvals,
+                                        const uint32_t *d_resource_in) {
     if (d_res_special.n < (size_t)nres + 1) {
         d_res_special.alloc((size_t)nres + 1);
         SGA_HIP_CHECK(hipMemset(d_res_special.p, 0, d_res_special.bytes()));
@@ -6632,6 +6781,7 @@ FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *
     f.in_flags = d_flags_in;
     f.in_param = d_param_in;
     f.pvals = d_pvals;
+    f.in_resource = d_resource_in;
     return f;
 }
 
@@ -6744,7 +6894,7 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
             continue;
         }
         FlowScratch fsc = special_scratch(sc, d_kind.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
-                                          has_list ? d_pvals.p : nullptr);
+                                          has_list ? d_pvals.p : nullptr, d_resid.p);
         const uint64_t *evp = fsc.ev_param;
         hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, stream, st, fsc, d_kind.p, d_resid.p, d_ts.p, lo, d_acq.p,
                            d_flags.p, param ? d_param.p : nullptr, (uint32_t)m, sc.keys[0], sc.pay[0], d_dec.p, d_wait.p);
@@ -6764,6 +6914,10 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         if ((h_prules.empty() && h_cbs.empty()) || !pseg_on()) fsc_p.pseg = nullptr;
         hipLaunchKernelGGL(k_lflows, dim3((fthreads + kT - 1) / kT), dim3(kT), 0, stream, st,
                            (int64_t)cfg.statistic_max_rt, fsc_p, pay, keys, lo, d_rt.p, evp, d_dec.p, d_wait.p);
+        if (has_groups)  // the RELATE groups k_lflows left to a wave each
+            hipLaunchKernelGGL(k_lgroup, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, (uint32_t)(m / kGroupEvents)))),
+                               dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo, d_rt.p, d_dec.p,
+                               d_wait.p);
         launch_pseg(st, fsc_p, pay, keys, lo, d_rt.p, evp, d_dec.p, d_wait.p, (uint32_t)m, stream);
         if (st.lru_res) {
             hipLaunchKernelGGL(k_llru, dim3(64), dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo,
@@ -6873,7 +7027,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     lru_prepare(d_kind_in, d_resource, flags_p, param_p, d_param_values, m, s);  // CacheMap capacity
     FlowState st = state();
     st.gate = d_gate.p;
-    FlowScratch gsc = special_scratch(sc, d_kind_in, flags_p, param_p, d_param_values);
+    FlowScratch gsc = special_scratch(sc, d_kind_in, flags_p, param_p, d_param_values, d_resource);
     gsc.gate = d_gate.p;
     hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, s, st, gsc, d_kind_in, d_resource, d_ts_off, ts_base, d_acquire,
                        flags_p, param_p, m, gsc.keys[0], gsc.pay[0], d_decision, wait_p);
@@ -6893,6 +7047,9 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     if ((h_prules.empty() && h_cbs.empty()) || !pseg_on()) gsc.pseg = nullptr;
     hipLaunchKernelGGL(k_lflows, dim3((fthreads + kT - 1) / kT), dim3(kT), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc,
                        pay, keys, ts_base, rt_p, evp, d_decision, wait_p);
+    if (has_groups)  // known on the host from the rule load: no launch without RELATE rules
+        hipLaunchKernelGGL(k_lgroup, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, m / kGroupEvents))), dim3(64), 0,
+                           s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p, d_decision, wait_p);
     launch_pseg(st, gsc, pay, keys, ts_base, rt_p, evp, d_decision, wait_p, m, s);
     if (st.lru_res) {
         hipLaunchKernelGGL(k_llru, dim3(64), dim3(64), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p,

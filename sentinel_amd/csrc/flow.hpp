@@ -31,6 +31,9 @@ constexpr int kNodeBor = kNodeSec + 2 * kMB;      // 2 x 2 (start, PASS)
 constexpr int kNodeMin = kNodeBor + 4;            // 60 x 8
 constexpr int kNodeThreads = kNodeMin + 60 * kMB; // curThreadNum
 constexpr int kNodeLastFetch = kNodeThreads + 1;  // StatisticNode.lastFetchTime (-1 initially)
+// nonzero once ClusterBuilderSlot.entry has run for the resource (its ClusterNode exists: a kind 0 / 2 / 3
+// event, whatever its outcome; ClusterBuilderSlot.java:70-100).  RELATE rules on other resources read it.
+constexpr int kNodeEntered = kNodeThreads + 2;
 constexpr int kNodeWords = kNodeThreads + 4;      // 504 words = 4032 B (64-B aligned)
 
 struct FlowRuleDev {    // one rater (TrafficShapingController) + its FlowRule fields
@@ -46,7 +49,11 @@ struct FlowRuleDev {    // one rater (TrafficShapingController) + its FlowRule f
     // rule's flowId (-1: no such cluster rule -> NO_RULE_EXISTS), resolved on the host before a batch
     int32_t cluster, cfallback;
     int64_t cflow;
-    int32_t cslot, cpad;
+    int32_t cslot;
+    // FlowRule.strategy (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116): 0 =
+    // DIRECT, the rater reads the resource's own node; otherwise RELATE, refResource's dense id + 1 -- nres + 1
+    // for a refResource that is no resource of the engine (its ClusterNode never exists: the rule passes)
+    uint32_t rel;
 };
 
 struct ParamRuleDev {
@@ -84,8 +91,9 @@ struct ResDev {
     uint32_t cb_off, n_cbs;
     uint32_t fast;   // bit0: single QPS Default/WarmUp rule, no param rules, no breakers;
                      // bit1: the resource has a parameter thread-count map (sticky)
-    uint32_t pad;
+    uint32_t group;  // leader (smallest member id) of the resource's RELATE group, kNoGroup: ungrouped
 };
+constexpr uint32_t kNoGroup = 0xFFFFFFFFu;  // SGA_REF_NONE
 
 // (rule, value) -> {time, tokens} for ParameterMetric rule maps; (resource, value) -> thread count
 struct alignas(32) PEntry {
@@ -134,6 +142,7 @@ struct FlowState {
     PEntry *ttab;      // thread-count maps
     uint32_t pmask, tmask;
     uint32_t nres;
+    uint32_t has_groups;  // the loaded FlowRules couple resources (RELATE): ResDev::group is read
     uint32_t *overflow;  // set when a param table is full (bit kOvfMissingEntry: a device check failed)
     // embedded cluster token server for cluster-mode FlowRules (sga_set_cluster_server 1)
     ClusterState cst;
@@ -240,6 +249,10 @@ struct FlowScratch {
     uint32_t epoch = 0;
     const uint8_t *in_kind = nullptr, *in_flags = nullptr;
     const uint64_t *in_param = nullptr, *pvals = nullptr;
+    // every event's resource as submitted: a RELATE group's events are sorted under the group's leader, and
+    // its replay takes each event's own resource from here
+    const uint32_t *in_resource = nullptr;
+    uint32_t *group = nullptr;  // flows of RELATE groups too long for their k_lflows lane (count in counters[15], k_lgroup)
 };
 
 void print_heavy_prof();  // SGA_HEAVY_PROF=1 diagnostics (flow.hip)
@@ -302,6 +315,10 @@ struct FlowEngine {
     std::vector<CbDev> h_cbs;
     std::vector<sga_degrade_rule> h_cb_src;
     std::vector<ResDev> h_res;
+    // RELATE groups (load_flow_rules): each resource's leader or kNoGroup; any: a launch of k_lgroup per chunk
+    std::vector<uint32_t> h_group;
+    bool has_groups = false;
+    int group_of(uint32_t resource, uint32_t *leader) const;
     uint32_t next_prule_id = 0;
     // staging for host API
     DevBuf<uint8_t> d_kind, d_flags;
@@ -335,7 +352,7 @@ struct FlowEngine {
                const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
                int32_t *wait_ms, const uint64_t *pvals = nullptr, size_t npvals = 0);
     FlowScratch special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
-                                const uint64_t *d_param_in, const uint64_t *d_pvals);
+                                const uint64_t *d_param_in, const uint64_t *d_pvals, const uint32_t *d_resource_in);
     DevBuf<uint64_t> d_pvals;  // values of Collection / array arguments (SGA_EV_PARAM_LIST)
     // the same over device buffers, asynchronous on s: one chunk of n <= max_batch events
     // small host batches (<= kSmallEvents events, <= kSmallWords argument words, no SystemRule check): one

@@ -4,7 +4,7 @@ Same names and argument meaning as the Java API the engine replaces:
   SphU.entry(resource, EntryType, batchCount, args...)  CORE/SphU.java:84-208  -> LocalSentinel.entry / submit
   Entry.exit(count, args...)                              CORE/Entry.java:86-111  -> Entry.exit
   Tracer.traceEntry(Throwable, Entry)                     CORE/Tracer.java:86-110 -> Entry.trace_error
-  FlowRuleManager.loadRules       CORE/slots/block/flow/FlowRuleManager.java:125-127
+  FlowRuleManager.loadRules       CORE/slots/block/flow/FlowRuleManager.java:125-127 (strategy DIRECT / RELATE)
   ParamFlowRuleManager.loadRules  PF/slots/block/flow/param/ParamFlowRuleManager.java:52
   DegradeRuleManager.loadRules    CORE/slots/block/degrade/DegradeRuleManager.java:108
   SystemRuleManager.loadRules     CORE/slots/system/SystemRuleManager.java:114-300 (SystemSlot, inbound only)
@@ -352,6 +352,14 @@ class LocalSentinel:
         out.sort(key=lambda m: (m.timestamp, self.ids.get(m.resource, ENTRY_NODE)))
         return out
 
+    def group_of(self, resource) -> int:
+        """Leader (smallest resource id) of the group the loaded RELATE FlowRules put `resource` in, or
+        SGA_REF_NONE when none couples it.  A group's events are decided in arrival order by one lane."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        leader = C.c_uint32()
+        check(_lib.load().sga_flow_group_of(self.engine.handle, rid, C.byref(leader)), self.engine.handle, "groupOf")
+        return int(leader.value)
+
     def circuit_breaker_state(self, resource, k: int = 0) -> int:
         rid = resource if isinstance(resource, int) else self.ids[resource]
         return _lib.load().sga_circuit_breaker_state(self.engine.handle, rid, k)
@@ -393,8 +401,16 @@ class FlowRuleManager:
             a.control_behavior = r.control_behavior
             a.warm_up_period_sec = r.warm_up_period_sec
             a.max_queueing_time_ms = r.max_queueing_time_ms
-            # non-default limitApp / RELATE / CHAIN are not served by the engine: rejected as invalid
+            # non-default limitApp and CHAIN are not served by the engine: rejected as invalid (the engine
+            # refuses strategy 2 itself).  RELATE (FlowRuleChecker.java:96-116) names its refResource by dense
+            # id -- SGA_REF_NONE for a name this sentinel has no resource for: its ClusterNode never exists, so
+            # the rule never blocks; a blank refResource is invalid (FlowRuleUtil.checkStrategyField)
             a.strategy = r.strategy if r.limit_app == RuleConstant.LIMIT_APP_DEFAULT else -1
+            if a.strategy == RuleConstant.STRATEGY_RELATE:
+                if r.ref_resource is None or not r.ref_resource.strip():
+                    a.strategy = -1
+                else:
+                    a.ref_resource = self.s.ids.get(r.ref_resource, _lib.SGA_REF_NONE)
             if r.cluster_mode:
                 cc = r.cluster_config
                 a.cluster_mode = 1
