@@ -1768,41 +1768,8 @@ __device__ __forceinline__ uint32_t bucket_delta(uint32_t t, uint32_t W, uint32_
     return (uint32_t)q;
 }
 
-// Per batch: r0 and 1/W of every window-length code (the dense flowId table's wcode), and the
-// precheck: no hot rule's window may hold a bucket newer than the batch's first request (batches
-// submitted out of time order), as the closed form needs each run's bucket to be the newest.
-__global__ __launch_bounds__(kThreads) void k_hot_precheck(ClusterState st, BatchScratch sc, const ReqIn in,
-                                                           int64_t ts_base, uint32_t n, int pipelined) {
-    if (blockIdx.x == 0 && st.dense_n) {
-        const uint32_t W = st.wtab[threadIdx.x];
-        WConst wc;
-        wc.W = W;
-        wc.r0 = (uint32_t)(ts_base % (int64_t)W);
-        wc.inv = 1.0 / (double)W;
-        sc.wconst[threadIdx.x] = wc;
-    }
-    const uint32_t h = blockIdx.x * kThreads + threadIdx.x;
-    if (h < (uint32_t)kHot) {  // the prioritized-range table of this batch (k_prio_rank fills it)
-        sc.plo[h] = 0;
-        sc.phi[h] = 0;
-    }
-    if (h >= hot_count(sc) || n == 0) return;
-    const int64_t W = (int64_t)sc.hot_ctl[2];
-    const int64_t t0 = ts_base + (int64_t)in.ts_at(0);
-    // Pipelined batches: the window starts read here may still be written by the earlier batch being
-    // decided.  That batch writes buckets at its own times only, so the answer is the same either way
-    // when this batch starts no earlier than every earlier batch's latest time; otherwise no hot path.
-    if (pipelined && h == 0 && t0 < (int64_t)*sc.tmax_all) atomicOr(&sc.counters[CTL_FLAGS], kFlagState);
-    const int64_t ws0 = t0 - t0 % W;
-    const uint32_t s = sc.hot_slot[h];
-    const SlotParam P = st.param[s];
-    bool bad = P.W != (int32_t)W || !P.active || P.S <= 1 || P.S > 64;
-    const Rec R = rec_of(st, P);
-    for (int j = 0; j < P.S && !bad; ++j) {
-        const int64_t w = R.start(j);
-        if (w != kAbsent && w > ws0) bad = true;
-    }
-    if (bad) atomicOr(&sc.counters[CTL_FLAGS], kFlagState);
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // k_hot_key: one workgroup per kHotSeg-request rank segment, one wave per 1024-request compaction
@@ -1817,8 +1784,11 @@ __global__ __launch_bounds__(kThreads) void k_hot_precheck(ClusterState st, Batc
 // row is written.  At a hot bucket boundary inside the segment the wave's counts before it are
 // snapshot into a pre row (earlier waves' totals added after the scan); the boundary table records
 // where every bucket of the batch starts.
-// Pass 1 of the batch is this kernel again with no hot rules (launched always, returns at once
-// unless a fallback flag is up): every valid request becomes a cold element.
+// Pass 1 of the batch is this kernel again with no hot rules (launched always, with few workgroups, which
+// return at once unless a fallback flag is up): every valid request becomes a cold element.
+// Pass 0 also makes the batch's window constants (each workgroup its own copy in LDS), carries the precheck
+// (hot_precheck, in workgroups of its own after the segments') and adds up the batch's totals, which pass 1's
+// first wave turns into the control words (hot_key_pass): no launch of their own for any of them.
 // Software pipeline over chunks of kH1Chunk rounds with three register buffers used in rotation
 // (the loop is unrolled three times, so no buffer is copied: copying a register a load is still
 // writing waits for that load).  While chunk c is processed, the table lookups of chunk c + 1 and
@@ -1829,11 +1799,50 @@ constexpr uint32_t kPsGroups = 256;  // the prioritized sort's groups of rank se
 constexpr int kKeyWaves = kHotSeg / kSubSeg;  // 8: one rank segment per workgroup
 constexpr int kKeyThreads = kKeyWaves * 64;
 static_assert(kKeyWaves == kSubPerSeg, "one wave per compaction segment");
+// The precheck of a hot-path batch, run by kPreWgs workgroups of their own at the end of pass 0's grid (one
+// hot id per thread): no hot rule's window may hold a bucket newer than the batch's first request (batches
+// submitted out of time order), as the closed form needs each run's bucket to be the newest.  Returns
+// kFlagState or 0.  The flag may so go up while the key workgroups already rank their requests: pass 1
+// re-classifies every request whenever a fallback flag is up, and what pass 0 leaves behind is what it
+// leaves behind under the other fallback flags.
+// Not inside the key workgroups (hot id = segment * kKeyThreads + thread was tried): the segments are a
+// whole number of rounds of the device's workgroup slots, so a key workgroup that is late makes the pass
+// late, and the check's code in the key workgroups' path cost the streaming loop scalar registers --
+// 167 to 172 us against 158 without it (C3, MI355X).  Workgroups of their own run beside the last round.
+constexpr uint32_t kPreWgs = kHot / kKeyThreads;
+constexpr int kPreChunk = 16;  // window starts loaded before any is looked at
+__device__ __forceinline__ uint32_t hot_precheck(const ClusterState &st, const BatchScratch &sc, const ReqIn &in,
+                                                 int64_t ts_base, uint32_t h, int pipelined) {
+    if (h >= hot_count(sc)) return 0u;
+    uint32_t flag = 0;
+    const int64_t W = (int64_t)sc.hot_ctl[2];
+    const int64_t t0 = ts_base + (int64_t)in.ts_at(0);
+    // Pipelined batches: the window starts read here may still be written by the earlier batch being
+    // decided.  That batch writes buckets at its own times only, so the answer is the same either way
+    // when this batch starts no earlier than every earlier batch's latest time; otherwise no hot path.
+    if (pipelined && h == 0 && t0 < (int64_t)*sc.tmax_all) flag = kFlagState;
+    const int64_t ws0 = t0 - t0 % W;
+    const SlotParam P = st.param[sc.hot_slot[h]];
+    bool bad = P.W != (int32_t)W || !P.active || P.S <= 1 || P.S > 64;
+    const Rec R = rec_of(st, P);
+    for (int j0 = 0; j0 < P.S && !bad; j0 += kPreChunk) {
+        int64_t w[kPreChunk];
+#pragma unroll
+        for (int k = 0; k < kPreChunk; ++k) w[k] = R.start(min(j0 + k, P.S - 1));
+#pragma unroll
+        for (int k = 0; k < kPreChunk; ++k)
+            if (j0 + k < P.S && w[k] != kAbsent && w[k] > ws0) bad = true;
+    }
+    return bad ? (uint32_t)kFlagState : flag;
+}
+
 struct KeyShared {
     WConst wcs[256];
     uint16_t cnt[kKeyWaves][kHot];  // per wave: hot requests so far per hot id
     uint32_t s_np[kKeyWaves], s_bd[kKeyWaves], s_tm[kKeyWaves];
     uint32_t s_bmin, s_bmax;  // hot buckets whose first request lies inside the segment (not at its start)
+    uint32_t s_last;          // this workgroup took pass 1's last ticket
+    uint32_t s_nc[kKeyWaves];
     union {
         uint32_t hist0[2][256];      // per sort tile of the segment: the first radix digit's counts
         uint32_t phist[kPartBins];   // partition mode: the segment's cold elements per slot bin
@@ -1843,7 +1852,7 @@ struct KeyShared {
 template <int kPass, bool kDense, bool kNT = false, bool kPk = false>
 __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, const BatchScratch &sc, const ReqIn in,
                                         int64_t ts_base, uint32_t n, uint64_t *__restrict__ out, int dbg,
-                                        int d0, uint32_t *__restrict__ hist, uint32_t ntiles) {
+                                        int d0, uint32_t *__restrict__ hist, uint32_t ntiles, const uint32_t seg) {
     const int64_t *__restrict__ flow_id = in.flow;
     const int32_t *__restrict__ acquire = in.acq;
     const uint8_t *__restrict__ prio = in.prio;
@@ -1857,16 +1866,18 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
     const uint32_t dmask = (1u << d0) - 1u;
     auto &cnt = sh.cnt;
     uint32_t *s_np = sh.s_np, *s_bd = sh.s_bd;
-    const uint32_t flags0 = sc.counters[CTL_FLAGS];
-    // pass 0 decides nothing when the precheck refused the hot path; pass 1 (re-classifying every request as
-    // cold) runs after a refusal or a fallback flag of pass 0
-    if (kPass == 0 && (flags0 & kFlagState)) return;
-    if (kPass == 1 && !(flags0 & (kFlagRerun | kFlagState))) return;
     const uint32_t nhot = kPass == 0 ? hot_count(sc) : 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t lt = lanemask_lt64(lane);
-    if (kDense)
-        for (int k = threadIdx.x; k < 256; k += kKeyThreads) wcs[k] = sc.wconst[k];  // window-length codes
+    if (kDense)  // r0 and 1/W of every window-length code (the dense flowId table's wcode)
+        for (int k = threadIdx.x; k < 256; k += kKeyThreads) {
+            const uint32_t W = st.wtab[k];
+            WConst wc;
+            wc.W = W;
+            wc.r0 = (uint32_t)(ts_base % (int64_t)W);
+            wc.inv = 1.0 / (double)W;
+            wcs[k] = wc;
+        }
     for (int k = threadIdx.x; k < (pl ? kPartBins : 2 * 256); k += kKeyThreads) sh.phist[k] = 0;
     if (nhot) {
         uint4 *cz = reinterpret_cast<uint4 *>(&cnt[0][0]);
@@ -1877,7 +1888,6 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
         sh.s_bmax = 0u;
     }
     __syncthreads();
-    const uint32_t seg = blockIdx.x;
     const uint32_t sub = seg * kKeyWaves + wave;
     const uint32_t ubase = sub * kSubSeg;
     const bool active = ubase < n;
@@ -2147,14 +2157,10 @@ bdmax = wave_max_u32(bdmax);
                 row[k] = run;  // this segment's count row
             }
         }
-        if (threadIdx.x == 0) {  // reduced by k_hot_mode: thousands of same-address atomics would serialize
-            uint32_t a = 0, m = 0;
-            for (int w = 0; w < kKeyWaves; ++w) {
-                a += s_np[w];
-                m = max(m, s_bd[w]);
-            }
+        if (threadIdx.x == 0) {  // the segment's prioritized hot requests (k_psort_scatter)
+            uint32_t a = 0;
+            for (int w = 0; w < kKeyWaves; ++w) a += s_np[w];
             sc.seg_stat[kSegStat * seg] = a;
-            sc.seg_stat[kSegStat * seg + 1] = m;
         }
         __syncthreads();
         if (active) {
@@ -2202,17 +2208,38 @@ bdmax = wave_max_u32(bdmax);
             __syncthreads();
         }
     }
-    {  // the segment's latest request time (offset from ts_base): k_hot_mode keeps the maximum over batches
-tmax_l = wave_max_u32(tmax_l);
-        if (lane == 0) sh.s_tm[wave] = tmax_l;
+    {  // the segment's share of the batch's totals: cold elements, prioritized hot requests, largest hot bucket
+       // delta, latest request time (offset from ts_base).  Pass 0 adds them to one of kKeyStripes stripes of
+       // ktot (no-return atomics; on one address the thousands of them would serialise), which pass 1's first
+       // workgroup sums (hot_key_pass); pass 1 itself has only its cold elements to count.
+        tmax_l = wave_max_u32(tmax_l);
+        if (lane == 0) {
+            sh.s_tm[wave] = tmax_l;
+            sh.s_nc[wave] = nc;  // 0 in a wave past the batch's end
+        }
         __syncthreads();
         if (threadIdx.x == 0) {
-            uint32_t m = 0;
-            for (int w = 0; w < kKeyWaves; ++w) m = max(m, sh.s_tm[w]);
-            sc.seg_stat[kSegStat * seg + 2] = m;
+            uint32_t tm = 0, a = 0, p = 0, bd = 0;
+            for (int w = 0; w < kKeyWaves; ++w) {
+                tm = max(tm, sh.s_tm[w]);
+                a += sh.s_nc[w];
+                if (nhot) {
+                    p += s_np[w];
+                    bd = max(bd, s_bd[w]);
+                }
+            }
+            if (kPass == 0) {
+                uint32_t *kt = sc.ktot + (seg % kKeyStripes) * kKeyStripeWords;
+                if (a) atomicAdd(&kt[0], a);
+                if (p) atomicAdd(&kt[1], p);
+                if (bd) atomicMax(&kt[2], bd);
+                if (tm) atomicMax(&kt[3], tm);
+            } else if (a) {
+                atomicAdd(&sc.counters[CTL_NSORT], a);
+            }
         }
     }
-    if (lane == 0) sc.tile_nc[sub] = active ? nc : 0u;  // totals: k_hot_mode
+    if (lane == 0) sc.tile_nc[sub] = active ? nc : 0u;
     if (pl) {  // the segment's bin counts (one contiguous row; k_part_colscan scans the columns)
         __syncthreads();
         for (uint32_t k = threadIdx.x; k < (uint32_t)kPartBins; k += kKeyThreads)
@@ -2368,65 +2395,93 @@ __global__ __launch_bounds__(kKeyThreads) void k_part_scatter(BatchScratch sc, u
     }
 }
 
+// Pass 0: one workgroup per rank segment.  Pass 1 (launched always, few workgroups): its first wave sums pass
+// 0's totals (ktot, one stripe per lane; zeroed for the next batch) into the control words -- the batch's
+// path and element counts -- and keeps the latest request time of every batch; unless a fallback flag is up
+// there is nothing else to do.  With a flag up the workgroups take the segments in turn, every valid request
+// becoming a cold element, and the last workgroup to finish (a ticket after a release fence; nobody waits)
+// writes the batch's words: no hot path, the cold elements pass 1 counted.
+template <int kPass, bool kDense, bool kNT, bool kPk>
+__device__ __forceinline__ void hot_key_pass(KeyShared &sh, const ClusterState &st, const BatchScratch &sc,
+                                             const ReqIn &in, int64_t ts_base, uint32_t n, uint64_t *__restrict__ out,
+                                             int dbg, int d0, uint32_t *__restrict__ hist, uint32_t ntiles,
+                                             int pipelined) {
+    const uint32_t nseg = (n + kHotSeg - 1) / kHotSeg;
+    if (kPass == 0) {
+        if (blockIdx.x >= nseg) {  // the precheck's workgroups, after the segments'
+            const uint32_t fl = hot_precheck(st, sc, in, ts_base, (blockIdx.x - nseg) * kKeyThreads + threadIdx.x,
+                                             pipelined);
+            if (fl) atomicOr(&sc.counters[CTL_FLAGS], fl);
+            return;
+        }
+        hot_key<0, kDense, kNT, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles, blockIdx.x);
+        return;
+    }
+    // the flags are final once pass 0 is done: every workgroup of pass 1 takes the same way
+    const uint32_t f = sc.counters[CTL_FLAGS];
+    const bool rerun = (f & (kFlagRerun | kFlagState)) != 0;
+    if (blockIdx.x == 0 && threadIdx.x < (uint32_t)kKeyStripes) {
+        static_assert(kKeyStripes == 64, "one stripe per lane of the first wave");
+        uint32_t *kt = sc.ktot + threadIdx.x * kKeyStripeWords;
+        uint32_t ns = kt[0], np = kt[1], bd = kt[2], tm = kt[3];
+        kt[0] = kt[1] = kt[2] = kt[3] = 0;
+        ns = wave_sum_u32(ns);
+        np = wave_sum_u32(np);
+        bd = wave_max_u32(bd);
+        tm = wave_max_u32(tm);
+        if (threadIdx.x == 0) {
+            // the latest request time of every batch classified so far (pipelined prechecks)
+            atomicMax(sc.tmax_all, (unsigned long long)(ts_base + (int64_t)tm));
+            if (!rerun) {
+                sc.counters[CTL_NSORT] = ns;  // the compaction segments hold the cold elements only
+                sc.counters[CTL_NPRIO] = np;
+                sc.counters[CTL_NCOLD] = ns;
+                sc.counters[CTL_BDHI] = bd;
+                sc.counters[CTL_MODE] = hot_count(sc) ? 1u : 0u;
+            }
+        }
+    }
+    if (!rerun) return;
+    for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+        hot_key<1, kDense, kNT, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles, seg);
+        __syncthreads();  // the segment's LDS reads are done before the next one clears it
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) sh.s_last = atomicAdd(&sc.counters[CTL_KTICKET], 1u) == gridDim.x - 1;
+    __syncthreads();
+    if (!sh.s_last || threadIdx.x != 0) return;
+    __threadfence();
+    const uint32_t ns = ld_agent(&sc.counters[CTL_NSORT]);  // every workgroup's cold elements (atomic adds)
+    sc.counters[CTL_NCOLD] = ns;
+    sc.counters[CTL_NPRIO] = 0;
+    sc.counters[CTL_BDHI] = 0;
+    sc.counters[CTL_MODE] = 0;
+    sc.counters[CTL_KTICKET] = 0;
+    if (f & kFlagState) {
+        // the precheck's refusal may have come while pass 0 ran: the batch reports what a refusal before
+        // pass 0 does (no other flag, no bucket words)
+        sc.counters[CTL_FLAGS] = kFlagState;
+        sc.counters[CTL_BDLO] = 0;
+        sc.counters[CTL_NPRE] = 0;
+    }
+}
+
 // Dense flowId table (the production layout): 4 waves per SIMD, two workgroups per CU.  kPk: packed requests.
 template <int kPass, bool kNT = false, bool kPk = false>
 __global__ __launch_bounds__(kKeyThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_hot_key_dense(
     ClusterState st, BatchScratch sc, ReqIn in, int64_t ts_base, uint32_t n, uint64_t *__restrict__ out, int dbg,
-    int d0, uint32_t *__restrict__ hist, uint32_t ntiles) {
+    int d0, uint32_t *__restrict__ hist, uint32_t ntiles, int pipelined) {
     __shared__ KeyShared sh;
-    hot_key<kPass, true, kNT, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles);
+    hot_key_pass<kPass, true, kNT, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles, pipelined);
 }
 // Hashed flowId table (sparse flowIds): the probe loop needs more registers.
 template <int kPass, bool kPk = false>
 __global__ __launch_bounds__(kKeyThreads) void k_hot_key_hash(
     ClusterState st, BatchScratch sc, ReqIn in, int64_t ts_base, uint32_t n, uint64_t *__restrict__ out, int dbg,
-    int d0, uint32_t *__restrict__ hist, uint32_t ntiles) {
+    int d0, uint32_t *__restrict__ hist, uint32_t ntiles, int pipelined) {
     __shared__ KeyShared sh;
-    hot_key<kPass, false, false, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles);
-}
-
-// The batch's path and element counts: sums over the compaction segments and the rank segments
-// (one workgroup).
-__global__ __launch_bounds__(1024) void k_hot_mode(BatchScratch sc, uint32_t nsub, uint32_t nseg, int64_t ts_base) {
-    __shared__ uint32_t red[4][16];
-    const uint32_t f = sc.counters[CTL_FLAGS];
-    const uint32_t nhot = (f & (kFlagRerun | kFlagState)) ? 0u : hot_count(sc);
-    uint32_t ns = 0, np = 0, bd = 0, tm = 0;
-    for (uint32_t k = threadIdx.x; k < nsub; k += 1024) ns += sc.tile_nc[k];
-    for (uint32_t k = threadIdx.x; k < nseg; k += 1024) {
-        if (nhot) {
-            np += sc.seg_stat[kSegStat * k];
-            bd = max(bd, sc.seg_stat[kSegStat * k + 1]);
-        }
-        tm = max(tm, sc.seg_stat[kSegStat * k + 2]);
-    }
-    ns = wave_sum_u32(ns);
-    np = wave_sum_u32(np);
-    bd = wave_max_u32(bd);
-    tm = wave_max_u32(tm);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = ns;
-        red[1][threadIdx.x >> 6] = np;
-        red[2][threadIdx.x >> 6] = bd;
-        red[3][threadIdx.x >> 6] = tm;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0, m = 0, t = 0;
-        for (int w = 0; w < 16; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-            m = max(m, red[2][w]);
-            t = max(t, red[3][w]);
-        }
-        // the latest request time of every batch classified so far (pipelined prechecks)
-        atomicMax(sc.tmax_all, (unsigned long long)(ts_base + (int64_t)t));
-        sc.counters[CTL_NSORT] = a;  // the compaction segments hold the cold elements only
-        sc.counters[CTL_NPRIO] = b;
-        sc.counters[CTL_NCOLD] = a;
-        sc.counters[CTL_BDHI] = m;
-        sc.counters[CTL_MODE] = nhot ? 1u : 0u;
-    }
+    hot_key_pass<kPass, false, false, kPk>(sh, st, sc, in, ts_base, n, out, dbg, d0, hist, ntiles, pipelined);
 }
 
 // Column prefix of the count rows over segments, in groups of kHotGroupRows rows.
@@ -4297,9 +4352,9 @@ size_t batch_scratch_bytes(size_t cap, uint32_t nslots_cap) {
     b += align_up(kHot * sizeof(double2));                                        // hthr
     b += align_up(cap * 4);                                                        // prank
     b += 3 * align_up(kHot * 4);                                                   // plo, phi, hot_tot
-    b += align_up(256 * sizeof(WConst));
     b += align_up(segs_alloc * kSegStat * 4);                                      // seg_stat
     b += align_up(64);                                                             // tmax_all
+    b += align_up(kKeyStripes * kKeyStripeWords * 4);                              // ktot
     b += align_up((size_t)kHotCand * 2 * 4);                                       // hot_cand
     b += align_up(segs_alloc * kPartBins * 4);                                     // phist
     b += align_up(((segs_alloc + kPartGroup - 1) / kPartGroup) * kPartBins * 4);   // pgrp
@@ -4373,9 +4428,10 @@ void batch_scratch_carve(BatchScratch &sc, void *base, size_t cap, uint32_t nslo
     sc.plo = (uint32_t *)take(kHot * 4);
     sc.phi = (uint32_t *)take(kHot * 4);
     sc.hot_tot = (uint32_t *)take(kHot * 4);
-    sc.wconst = (WConst *)take(256 * sizeof(WConst));
     sc.seg_stat = (uint32_t *)take(segs_alloc * kSegStat * 4);
     sc.tmax_all = (unsigned long long *)take(64);
+    sc.ktot = (uint32_t *)take(kKeyStripes * kKeyStripeWords * 4);
+    SGA_HIP_CHECK(hipMemset(sc.ktot, 0, kKeyStripes * kKeyStripeWords * 4));  // pass 1 keeps it zero
     sc.hot_cand = (uint32_t *)take((size_t)kHotCand * 2 * 4);
     sc.phist = (uint32_t *)take(segs_alloc * kPartBins * 4);
     sc.pgrp = (uint32_t *)take(((segs_alloc + kPartGroup - 1) / kPartGroup) * kPartBins * 4);
@@ -4446,7 +4502,7 @@ void hot_reset(const ClusterState &st, BatchScratch &sc, uint32_t nslots_cap, hi
                        dim3(256), 0, s, st, sc, nslots_cap);
 }
 
-// Hot path batch (kernels above): precheck -> classify (+ fallback re-classification) -> count
+// Hot path batch (kernels above): classify with the precheck (+ fallback re-classification) -> count
 // scan -> sort of the cold (and prioritized hot) elements -> cold runs / flows / results -> hot
 // runs (k_hot_flows) -> hot results in input order -> prioritized hot results -> next hot set.
 // Every kernel reads the batch's path from the control words, so no host synchronisation.
@@ -4487,7 +4543,7 @@ static int hot_key_bits(const ClusterState &st) {
 }
 
 // Stage 1 of a hot-path batch (reads only its inputs, the dense table and -- the precheck -- the hot
-// rules' window starts): the precheck, the key pass (in-segment ranks, cold elements), the count scans,
+// rules' window starts): the key pass (precheck, in-segment ranks, cold elements), the count scans,
 // the prioritized sort and the cold sort.  The result is in sc (CTL words, el[], pel[], hcode, hbase).
 // pipelined: an earlier batch may still be deciding (sga_request_tokens_device_pipelined); the precheck
 // then also refuses the hot path to a batch that starts before the latest time of any earlier batch.
@@ -4523,9 +4579,10 @@ static void classify_hot(const ClusterState &st, BatchScratch &sc, const ReqIn &
     const int bits = hot_key_bits(st);
     const uint32_t nseg = (n + kHotSeg - 1) / kHotSeg;
     const uint32_t ngroups = (nseg + kHotGroupRows - 1) / kHotGroupRows;
-    if (!clean) SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, CTL_WORDS * 4, s));
-    hipLaunchKernelGGL(k_hot_precheck, dim3(kHot / kThreads), dim3(kThreads), 0, s, st, sc, in, ts_base, n,
-                       pipelined ? 1 : 0);
+    if (!clean) {
+        SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, CTL_WORDS * 4, s));
+        SGA_HIP_CHECK(hipMemsetAsync(sc.ktot, 0, kKeyStripes * kKeyStripeWords * 4, s));
+    }
     // the key pass streams its inputs and cold elements non-temporally, so the dense table keeps more of L2
     // (158 against 166 us on MI355X; SGA_KEY_NT=0, an A/B knob, turns it off)
     static const bool key_nt = !(getenv("SGA_KEY_NT") && atoi(getenv("SGA_KEY_NT")) == 0);
@@ -4543,11 +4600,11 @@ static void classify_hot(const ClusterState &st, BatchScratch &sc, const ReqIn &
     const int d0 = sc.part_lb ? -sc.part_lb : (dsort <= 8 ? dsort : 0);
     const uint32_t ntiles_sort = (uint32_t)radix64_tiles(n);
     uint32_t *khist = sc.part_lb ? sc.phist : sc.radix.hist;
-    hipLaunchKernelGGL(hka, dim3(nseg), dim3(kKeyThreads), 0, s, st, sc, in, ts_base, n, out, fz_debug(), d0, khist,
-                       ntiles_sort);
-    hipLaunchKernelGGL(hkb, dim3(nseg), dim3(kKeyThreads), 0, s, st, sc, in, ts_base, n, out, fz_debug(), d0, khist,
-                       ntiles_sort);
-    hipLaunchKernelGGL(k_hot_mode, dim3(1), dim3(1024), 0, s, sc, nseg * kKeyWaves, nseg, ts_base);
+    hipLaunchKernelGGL(hka, dim3(nseg + kPreWgs), dim3(kKeyThreads), 0, s, st, sc, in, ts_base, n, out, fz_debug(), d0, khist,
+                       ntiles_sort, pipelined ? 1 : 0);
+    // pass 1 finds nothing to do unless a fallback flag is up: few workgroups, which take the segments in turn
+    hipLaunchKernelGGL(hkb, dim3(std::min<uint32_t>(nseg, 256)), dim3(kKeyThreads), 0, s, st, sc, in, ts_base, n, out,
+                       fz_debug(), d0, khist, ntiles_sort, 0);
     const bool ovl = hot_overlap() && !(fz_debug() & 16);
     sc.sched2 = ovl && !pipelined && hot_sched() == 2;
     if (sc.sched2) {

@@ -144,6 +144,8 @@ constexpr int kHotBuckets = 64;     // window buckets a batch may span on the ho
 constexpr int kHotGroupRows = 16;   // count rows per group of the column scan
 constexpr int kHotCand = 1 << 16;   // next-hot-set candidates gathered per batch
 constexpr int kSegStat = 4;         // seg_stat words per rank segment
+constexpr int kKeyStripes = 64;     // ktot: the key workgroups' totals are added to stripe segment % kKeyStripes,
+constexpr int kKeyStripeWords = 32; // a 128-byte line each
 // Cold partition (hot path): the cold elements are scattered once into kPartBins bins of consecutive
 // rule slots (slot >> part_lb), and k_cold_fused orders each bin in its workgroup (SURVEY hard part 4)
 constexpr int kPartBits = 11;
@@ -163,6 +165,8 @@ enum : int {
     CTL_BDHI = 24,       // largest hot bucket delta
     CTL_MODE = 25,       // 1: the batch runs the hot path
     CTL_HOTERR = 26,     // hot runs that needed a replay (never expected)
+    CTL_KTICKET = 27,    // workgroups of the fallback key pass done (the last one writes the batch's words and puts
+                         // it back to 0)
     CTL_WORDS = 64
 };
 enum : uint32_t {
@@ -234,9 +238,9 @@ struct BatchScratch {
     uint32_t *prank;          // per prioritized hot request (order of pel): its rank among its rule's requests
     uint32_t *plo, *phi;      // per hot id: its range in the prioritized region
     uint32_t *hot_tot;        // per hot id: requests in the batch
-    WConst *wconst;           // [256] per window-length code
-    uint32_t *seg_stat;       // per rank segment (kSegStat words): prioritized hot requests, largest hot bucket
-                              // delta, latest request time (offset)
+    uint32_t *seg_stat;       // per rank segment (kSegStat words): prioritized hot requests
+    uint32_t *ktot;           // [kKeyStripes][kKeyStripeWords] the key pass's totals: cold elements, prioritized hot
+                              // requests, largest hot bucket delta, latest request time (offset)
     unsigned long long *tmax_all;  // latest request time of every hot-path batch classified so far (precheck of
                                    // pipelined batches; shared by an engine's scratch sets)
     const uint64_t *el_sorted = nullptr, *pel_sorted = nullptr;  // stage 1's sorted cold / prioritized elements

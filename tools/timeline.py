@@ -1,5 +1,7 @@
-"""Prints one batch's kernel timeline (us from the batch's k_hot_precheck start) from a rocprofv3
-kernel-trace CSV: python3 tools/timeline.py trace.csv [batch index from the end, default 2]."""
+"""Prints one batch's kernel timeline (us from the batch's first kernel) from a rocprofv3
+kernel-trace CSV: python3 tools/timeline.py trace.csv [batch index from the end, default 2].
+A batch starts at its k_hot_precheck (builds that still launch one) or else at its first key pass
+(k_hot_key_dense<0 / k_hot_key_hash<0).  The last line is the next batch's first kernel."""
 import csv, re, sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
@@ -9,6 +11,8 @@ for r in rows:  # demangled names: keep the function name
     if m:
         r["Kernel_Name"] = m.group(1)
 starts = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("k_hot_precheck")]
+if not starts:
+    starts = [i for i, r in enumerate(rows) if re.match(r"k_hot_key_(dense|hash)<0", r["Kernel_Name"])]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 a, b = starts[-k], starts[-k + 1] if k > 1 else len(rows)
 t0 = int(rows[a]["Start_Timestamp"])
