@@ -526,6 +526,8 @@ __device__ __forceinline__ int64_t i64_hi(const int4 &v) {
 // ClusterMetricLeapArray.resetWindowTo), the valid buckets summed, the pass prefix and the
 // occupied (SHOULD_WAIT) count found over the exact Java predicates, and the current bucket's
 // seven counters stored once.  Returns false (nothing touched) when the run is not eligible.
+// Two forms, after the record's (cluster_exact.hpp): run_compact reads the 128-byte decision line,
+// run_wide the 64-bit header.  A rule's later runs reload the header (an L2 hit: the lane just wrote it).
 
 struct RunIn {
     uint32_t j0, n, cp_tot, p0;
@@ -533,146 +535,23 @@ struct RunIn {
     uint32_t bd;  // bucket delta of the run (its bucket = ts_base / W + bd)
 };
 
-// A rule's record between its runs (cold flows): the record header as the lane's last run left it
-// -- the (start, PASS) pairs, the occupy state, the cached counter group with its tag and the
-// threshold -- so the rule's later runs issue no record loads (one memory round trip per rule
-// instead of one per run).  have = false: load from the record.
-#ifndef SGA_CARRY_PAIRS
-#define SGA_CARRY_PAIRS 0
-#endif
-// 1: later runs of a rule take the pairs from registers (64 more VGPRs live across runs: two waves per
-// SIMD); 0: they reload the header (an L2 hit: the lane just wrote it), and the kernel fits three
-constexpr bool kCarryPairs = SGA_CARRY_PAIRS;
-template <int kMaxPairs>
-struct RecCarry {
-    int4 sp[kMaxPairs > 0 ? kMaxPairs : 1];
-    int4 o0, o1;
-    int4 cg[3];  // cached group: (WAITING, BLOCK), (PASS_REQUEST, BLOCK_REQUEST), (OCCUPIED_PASS, OCCUPIED_BLOCK)
-    int4 meta;   // (tag, threshold)
-    bool have;
-};
-
 __device__ __forceinline__ double f64_hi(const int4 &v) { return __longlong_as_double(i64_hi(v)); }
+__device__ __forceinline__ int4 i4_of(int64_t lo, int64_t hi) {
+    return make_int4((int)(uint32_t)lo, (int)(uint32_t)((uint64_t)lo >> 32), (int)(uint32_t)hi,
+                     (int)(uint32_t)((uint64_t)hi >> 32));
+}
 
-// prio_before(k): prioritized requests among the run's first k (asked only when some prioritized
-// request is past the passing prefix).  kMaxPairs = 0: sampleCount above the register form, the
-// pairs are loaded one by one every run.  hdr_thr: the threshold is the record's copy (Rec::thr),
-// not thr_in (which the caller then did not load).
-#ifndef SGA_SKIP_GROUP
-#define SGA_SKIP_GROUP 0
-#endif
-constexpr bool kSkipGroup = SGA_SKIP_GROUP;  // profiling builds only (the array group then goes stale)
-#ifndef SGA_HDR_CACHE_ALL
-#define SGA_HDR_CACHE_ALL 0
-#endif
-constexpr bool kHdrCacheAll = SGA_HDR_CACHE_ALL;  // 1: every cold run rewrites the header's counter cache
-template <class PrioBefore, int kMaxPairs>
-__device__ __forceinline__ bool run_fast(const ClusterState &st, const SlotParam &P, const Rec &R, double thr_in,
-                                         bool hdr_thr, int64_t qbase, const RunIn &ri, PrioBefore prio_before,
-                                         RunOut &ro, RecCarry<kMaxPairs> &rc) {
-    // Cluster rules have intervalInMs = sampleCount x windowLengthInMs (checkClusterField), so every
-    // validity test below (isWindowDeprecated, getValidHead) gives the same answer for any time in
-    // the run's bucket: the bucket start stands in for the first request's time.
+// The decisions of a run, common to both forms.  In: the current bucket's counters c after the rotation,
+// the occupy state o after the rotation's transfer, the PASS sum bp of the other valid buckets, the valid
+// head's PASS.  waiting_others(): WAITING summed over the other valid buckets (only asked when a
+// prioritized request is past the passing prefix).  prio_before(k): prioritized requests among the run's
+// first k.  Out: c and o as the run leaves them, occ_dirty raised when o changed, ro filled.
+template <class PrioBefore, class WaitingOthers>
+__device__ __forceinline__ void run_decide(const ClusterState &st, const SlotParam &P, double thr, const RunIn &ri,
+                                           PrioBefore prio_before, WaitingOthers waiting_others, int64_t bp,
+                                           int64_t head, int64_t (&c)[CEV_N], SlotOcc &o, bool &occ_dirty,
+                                           RunOut &ro) {
     const int32_t a = ri.a;
-    const int64_t q = qbase + ri.bd;  // bucket number
-    const int64_t ws = q * P.W;
-    const int64_t t0 = ws;
-    const int64_t qs = div_pos(q, P.S);
-    const int cj = (int)(q - qs * P.S);
-    const int jh = cj + 1 == P.S ? 0 : cj + 1;  // LeapArray.getValidHead index ((t0 + W) / W) % S
-    // First run of a rule: the header's loads are issued before any is used (one memory latency, not
-    // one per dependent step), at clamped indices (a load under a branch is waited for before the
-    // branch closes, which would serialise them): the (start, PASS) pair of every bucket, the occupy
-    // state, the cached counter group and (tag, threshold) -- for S = 10 exactly the header's two
-    // 128-byte lines.  Later runs take them from registers.
-    const int4 *v = reinterpret_cast<const int4 *>(R.r);
-    const int4 *hv = reinterpret_cast<const int4 *>(R.cache());
-    if (!rc.have) {
-        const int4 *ov = reinterpret_cast<const int4 *>(&R.occ());
-        rc.o0 = ov[0];
-        rc.o1 = ov[1];
-        rc.cg[0] = hv[0];
-        rc.cg[1] = hv[1];
-        rc.cg[2] = hv[2];
-        rc.meta = hv[3];
-        if constexpr (kMaxPairs > 0) {
-#pragma unroll
-            for (int jj = 0; jj < kMaxPairs; ++jj) rc.sp[jj] = v[min(jj, P.S - 1)];
-        }
-    }
-    const double thr = hdr_thr ? f64_hi(rc.meta) : thr_in;
-    SlotOcc occ_ld;
-    occ_ld.occ_pass = i64_lo(rc.o0);
-    occ_ld.occ_preq = i64_hi(rc.o0);
-    occ_ld.has_occ = rc.o1.x;
-    occ_ld.pad = rc.o1.y;
-    int4 cur;  // the current bucket's pair
-    int64_t bp = 0, hstart = kAbsent, hpass = 0;
-    {
-        auto take = [&](int jj, const int4 &sp) {
-            const int64_t w = i64_lo(sp), pv = i64_hi(sp);
-            if (jj == jh) {
-                hstart = w;
-                hpass = pv;
-            }
-            if (jj != cj && w != kAbsent && !(t0 - w > (int64_t)P.interval)) bp += pv;
-        };
-        if constexpr (kMaxPairs > 0) {
-            cur = rc.sp[0];
-#pragma unroll
-            for (int jj = 1; jj < kMaxPairs; ++jj)
-                if (jj == cj) cur = rc.sp[jj];
-#pragma unroll
-            for (int jj = 0; jj < kMaxPairs; ++jj)
-                if (jj < P.S) take(jj, rc.sp[jj]);
-        } else {
-            cur = v[cj];
-            for (int jj = 0; jj < P.S; ++jj) take(jj, v[jj]);
-        }
-    }
-    const int64_t old = i64_lo(cur);
-    if (a <= 0 || (old != kAbsent && ws < old)) return false;
-    if (ri.cp_tot > 0 && (P.S <= 1 || 1000 / P.S <= 0)) return false;
-    const bool rot = old == kAbsent || ws > old;
-    int4 c01 = rc.cg[0], c23 = rc.cg[1], c45 = rc.cg[2];
-    const bool tag_was_cur = i64_lo(rc.meta) == old;
-    if (!rot && !tag_was_cur) {  // the current bucket's counters are not the cached group: the array
-        const int4 *cv = reinterpret_cast<const int4 *>(R.group(cj));
-        c01 = cv[0];
-        c23 = cv[1];
-        c45 = cv[2];
-    }
-    int64_t c[CEV_N];
-    SlotOcc o{0, 0, 0, 0};
-    bool occ_loaded = false, occ_dirty = false;
-    if (rot) {
-#pragma unroll
-        for (int k = 0; k < CEV_N; ++k) c[k] = 0;
-        if (old != kAbsent) {  // resetWindowTo + transferOccupyToBucket
-            o = occ_ld;
-            occ_loaded = true;
-            if (o.has_occ) {
-                c[CEV_OCCUPIED_PASS] += o.occ_pass;
-                c[CEV_PASS] += o.occ_pass;
-                c[CEV_PASS_REQUEST] += o.occ_preq;
-                o.occ_pass = 0;
-                o.occ_preq = 0;
-                o.has_occ = 0;
-                occ_dirty = true;
-            }
-        }
-    } else {
-        c[CEV_PASS] = i64_hi(cur);
-        c[CEV_WAITING] = i64_lo(c01);
-        c[CEV_BLOCK] = i64_hi(c01);
-        c[CEV_PASS_REQUEST] = i64_lo(c23);
-        c[CEV_BLOCK_REQUEST] = i64_hi(c23);
-        c[CEV_OCCUPIED_PASS] = i64_lo(c45);
-        c[CEV_OCCUPIED_BLOCK] = i64_hi(c45);
-    }
-    int64_t head;  // getValidHead after the rotation (the head is the current bucket when S == 1)
-    if (jh == cj) head = c[CEV_PASS];
-    else head = (hstart != kAbsent && !(t0 - hstart > (int64_t)P.interval)) ? hpass : 0;
     const int64_t s0 = bp + c[CEV_PASS];
     const uint32_t n = ri.n;
     const uint32_t f = pass_prefix(thr, P.isec, s0, a, n);
@@ -683,29 +562,7 @@ __device__ __forceinline__ bool run_fast(const ClusterState &st, const SlotParam
     const uint32_t np_after = ri.cp_tot - cpf;
     uint32_t cw = 0;
     if (np_after > 0) {
-        // WAITING over the same valid buckets (only runs with prioritized blocked requests read it;
-        // validity is re-tested per bucket, so any sampleCount works)
-        int64_t w0 = c[CEV_WAITING];
-        if constexpr (kMaxPairs > 0) {
-            // the S WAITING counters loaded together at clamped indices (one memory latency; a load per
-            // bucket behind its validity test waited S latencies, and about every wave has a lane here),
-            // validity from the pairs in registers
-            int64_t wv[kMaxPairs];
-#pragma unroll
-            for (int jj = 0; jj < kMaxPairs; ++jj) wv[jj] = R.group(min(jj, P.S - 1))[0];
-#pragma unroll
-            for (int jj = 0; jj < kMaxPairs; ++jj) {
-                const int64_t w = i64_lo(rc.sp[jj]);
-                if (jj < P.S && jj != cj && w != kAbsent && !(t0 - w > (int64_t)P.interval)) w0 += wv[jj];
-            }
-        } else {
-#pragma nounroll
-            for (int jj = 0; jj < P.S; ++jj) {
-                const int64_t w = R.start(jj);
-                if (jj != cj && w != kAbsent && !(t0 - w > (int64_t)P.interval)) w0 += R.cnt(CEV_WAITING, jj);
-            }
-        }
-        if (!occ_loaded) o = occ_ld;
+        const int64_t w0 = c[CEV_WAITING] + waiting_others();
         const double latest = div_isec((double)(s0 + (int64_t)f * a), P.isec);
         const double lim = st.max_occupy_ratio * thr;
         const int64_t occ0 = o.occ_pass;
@@ -735,50 +592,6 @@ __device__ __forceinline__ bool run_fast(const ClusterState &st, const SlotParam
     c[CEV_BLOCK] += (int64_t)nblk * a;
     c[CEV_BLOCK_REQUEST] += nblk;
     c[CEV_OCCUPIED_BLOCK] += (int64_t)(np_after - cw) * a;
-    // 16-byte stores: the (start, PASS) pair, the six other counters (one 48-byte group), the occupy state
-    {
-        const int64_t stv = rot ? ws : old;
-        auto i4 = [](int64_t lo, int64_t hi) {
-            return make_int4((int)(uint32_t)lo, (int)(uint32_t)((uint64_t)lo >> 32), (int)(uint32_t)hi,
-                             (int)(uint32_t)((uint64_t)hi >> 32));
-        };
-        reinterpret_cast<int4 *>(R.r)[cj] = i4(stv, c[CEV_PASS]);
-        rc.cg[0] = i4(c[CEV_WAITING], c[CEV_BLOCK]);
-        rc.cg[1] = i4(c[CEV_PASS_REQUEST], c[CEV_BLOCK_REQUEST]);
-        rc.cg[2] = i4(c[CEV_OCCUPIED_PASS], c[CEV_OCCUPIED_BLOCK]);
-        rc.meta.x = (int)(uint32_t)stv;  // the cache now holds bucket cj (the threshold word is stored back as loaded)
-        rc.meta.y = (int)(uint32_t)((uint64_t)stv >> 32);
-        int4 *cg = reinterpret_cast<int4 *>(R.group(cj));  // the array (authoritative) and the header's cache
-        int4 *ch = reinterpret_cast<int4 *>(R.cache());
-        if (!kSkipGroup) {
-            cg[0] = rc.cg[0];
-            cg[1] = rc.cg[1];
-            cg[2] = rc.cg[2];
-        }
-        // the header's cache: written when it must stay coherent (it already held this bucket) or when it is
-        // the policy (kHdrCacheAll); otherwise left alone -- its tag then names another bucket, and the run
-        // saves the partial write of the header's second line
-        if (kHdrCacheAll || (!rot && tag_was_cur)) {
-            ch[0] = rc.cg[0];
-            ch[1] = rc.cg[1];
-            ch[2] = rc.cg[2];
-            ch[3] = rc.meta;
-        }
-        if (occ_dirty) {
-            rc.o0 = i4(o.occ_pass, o.occ_preq);
-            rc.o1 = make_int4(o.has_occ, o.pad, rc.o1.z, rc.o1.w);  // the spare word stored back unchanged
-            int4 *ov = reinterpret_cast<int4 *>(&R.occ());
-            ov[0] = rc.o0;
-            ov[1] = rc.o1;
-        }
-        if constexpr (kMaxPairs > 0) {
-            const int4 np = i4(stv, c[CEV_PASS]);
-#pragma unroll
-            for (int jj = 0; jj < kMaxPairs; ++jj)
-                if (jj == cj) rc.sp[jj] = np;
-        }
-        rc.have = kCarryPairs && kMaxPairs > 0;
-    }
     ro.s0 = s0;
     ro.thr = thr;
     ro.isec = P.isec;
@@ -787,6 +600,248 @@ __device__ __forceinline__ bool run_fast(const ClusterState &st, const SlotParam
     ro.cw = cw;
     ro.wait = (uint16_t)(1000 / P.S);
     ro.mode = RUN_FAST;
+}
+
+// resetWindowTo + transferOccupyToBucket into a zeroed bucket
+__device__ __forceinline__ void occ_transfer(int64_t (&c)[CEV_N], SlotOcc &o, bool &occ_dirty) {
+    if (!o.has_occ) return;
+    c[CEV_OCCUPIED_PASS] += o.occ_pass;
+    c[CEV_PASS] += o.occ_pass;
+    c[CEV_PASS_REQUEST] += o.occ_preq;
+    o.occ_pass = 0;
+    o.occ_preq = 0;
+    o.has_occ = 0;
+    occ_dirty = true;
+}
+
+// hdr_thr: the threshold is the record's copy (Rec::thr), not thr_in (which the caller then did not load).
+// The compact form: one lane, eight 16-byte loads from the record's one decision line, all issued before
+// any is used.  Every test on window starts is a test on bucket numbers (cluster rules have intervalInMs =
+// sampleCount x windowLengthInMs, checkClusterField; a rule that has not takes the replay).  wide: the
+// record is wide (nothing decided: run_wide's).  A run whose result does not fit the line's fields returns
+// false before it stores anything; the exact replay then widens the record through Rec's accessors.
+template <class PrioBefore>
+__device__ __forceinline__ bool run_compact(const ClusterState &st, const SlotParam &P, const Rec &R, double thr_in,
+                                            bool hdr_thr, int64_t qbase, const RunIn &ri, PrioBefore prio_before,
+                                            RunOut &ro, bool &wide) {
+    int4 *lv = reinterpret_cast<int4 *>(R.ln());
+    int4 L[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) L[k] = lv[k];
+    const uint64_t b0 = (uint64_t)i64_lo(L[LN_BASE / 4]);
+    wide = (b0 & kLnWide) != 0;
+    if (wide) return false;
+    const int32_t a = ri.a;
+    const int64_t q = qbase + ri.bd;  // bucket number
+    if (a <= 0 || q < 0 || (int64_t)P.interval != (int64_t)P.S * (int64_t)P.W) return false;
+    if (ri.cp_tot > 0 && (P.S <= 1 || 1000 / P.S <= 0)) return false;
+    uint64_t b = b0;
+    if (!(b & kLnBaseSet)) {  // a fresh record: the base is chosen by its first bucket
+        const int64_t nb = ln_pick_base(q);
+        if (!ln_base_fits(nb)) return false;
+        b = (b & ~kLnBaseMask) | kLnBaseSet | (uint64_t)nb;
+    }
+    const int64_t base = ln_base(b);
+    if (!ln_delta_fits(q, base)) return false;
+    const uint32_t dq = ln_enc_delta(q, base);
+    const int64_t qs = div_pos(q, P.S);
+    const int cj = (int)(q - qs * P.S);
+    const int jh = cj + 1 == P.S ? 0 : cj + 1;  // LeapArray.getValidHead index ((t0 + W) / W) % S
+    const double thr = hdr_thr ? f64_hi(L[LN_THR / 4]) : thr_in;
+    // isWindowDeprecated: t0 - start > interval  <=>  bucket number difference > S (a newer bucket is valid)
+    auto valid = [&](uint32_t d) { return d != kLnNoBucket && !((int64_t)dq - (int64_t)d > (int64_t)P.S); };
+    uint32_t dcur = kLnNoBucket, pcur = 0, dh = kLnNoBucket, ph = 0;
+    int64_t bp = 0;
+    auto take = [&](int jj, int d, int pv) {
+        if (jj == cj) {
+            dcur = (uint32_t)d;
+            pcur = (uint32_t)pv;
+        } else if (valid((uint32_t)d)) {
+            bp += (int64_t)(uint32_t)pv;
+        }
+        if (jj == jh) {
+            dh = (uint32_t)d;
+            ph = (uint32_t)pv;
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < kLnPairs / 2; ++k) {  // buckets past S hold no bucket
+        take(2 * k, L[k].x, L[k].y);
+        take(2 * k + 1, L[k].z, L[k].w);
+    }
+    if (dcur != kLnNoBucket && dq < dcur) return false;  // time went backwards: detached bucket
+    const bool rot = dcur == kLnNoBucket || dq > dcur;
+    int64_t c[CEV_N];
+    SlotOcc o{(int64_t)(uint32_t)L[6].x, (int64_t)(uint32_t)L[6].y, (b & kLnHasOcc) ? 1 : 0, 0};
+    bool occ_dirty = false;
+    if (rot) {
+#pragma unroll
+        for (int k = 0; k < CEV_N; ++k) c[k] = 0;
+        if (dcur != kLnNoBucket) occ_transfer(c, o, occ_dirty);
+    } else {
+        c[CEV_PASS] = (int64_t)pcur;
+        if (ln_tag(b) == cj) {
+            c[CEV_WAITING] = (int64_t)(uint32_t)L[6].z;
+            c[CEV_BLOCK] = (int64_t)(uint32_t)L[6].w;
+            c[CEV_PASS_REQUEST] = (int64_t)(uint32_t)L[7].x;
+            c[CEV_BLOCK_REQUEST] = (int64_t)(uint32_t)L[7].y;
+            c[CEV_OCCUPIED_PASS] = (int64_t)(uint32_t)L[7].z;
+            c[CEV_OCCUPIED_BLOCK] = (int64_t)(uint32_t)L[7].w;
+        } else {  // the current bucket's counters are not the cached group: the array
+            const int4 *cv = reinterpret_cast<const int4 *>(R.group(cj));
+            const int4 c01 = cv[0], c23 = cv[1], c45 = cv[2];
+            c[CEV_WAITING] = i64_lo(c01);
+            c[CEV_BLOCK] = i64_hi(c01);
+            c[CEV_PASS_REQUEST] = i64_lo(c23);
+            c[CEV_BLOCK_REQUEST] = i64_hi(c23);
+            c[CEV_OCCUPIED_PASS] = i64_lo(c45);
+            c[CEV_OCCUPIED_BLOCK] = i64_hi(c45);
+        }
+    }
+    // getValidHead after the rotation (the head is the current bucket when S == 1)
+    const int64_t head = jh == cj ? c[CEV_PASS] : (valid(dh) ? (int64_t)ph : 0);
+    auto waiting_others = [&]() {
+        // the S WAITING counters loaded together at clamped indices (one memory latency; a load per bucket
+        // behind its validity test waited S latencies), validity from the pairs in registers
+        int64_t wv[kLnPairs], w0 = 0;
+#pragma unroll
+        for (int jj = 0; jj < kLnPairs; ++jj) wv[jj] = R.group(min(jj, P.S - 1))[0];
+#pragma unroll
+        for (int jj = 0; jj < kLnPairs; ++jj) {
+            const uint32_t d = (uint32_t)((jj & 1) ? L[jj / 2].z : L[jj / 2].x);
+            if (jj < P.S && jj != cj && valid(d)) w0 += wv[jj];
+        }
+        return w0;
+    };
+    run_decide(st, P, thr, ri, prio_before, waiting_others, bp, head, c, o, occ_dirty, ro);
+    if (!ln_count_fits(c[CEV_PASS]) || !ln_count_fits(o.occ_pass) || !ln_count_fits(o.occ_preq)) return false;
+    // a cached counter that does not fit only takes the tag away
+    bool cfit = true;
+#pragma unroll
+    for (int k = 1; k < CEV_N; ++k) cfit = cfit && ln_count_fits(c[k]);
+    uint64_t nb = ln_with_tag(b, cfit ? cj : -1);
+    nb = o.has_occ ? (nb | kLnHasOcc) : (nb & ~kLnHasOcc);
+    // 16-byte stores: the pair's piece, the base word's piece when it changed, the occupy counters and the
+    // cached group (all one line), and the six other counters into the array (one 48-byte group)
+    int4 pp = L[0];
+#pragma unroll
+    for (int k = 1; k < kLnPairs / 2; ++k)
+        if (k == (cj >> 1)) pp = L[k];
+    if (cj & 1) {
+        pp.z = (int)dq;
+        pp.w = (int)(uint32_t)c[CEV_PASS];
+    } else {
+        pp.x = (int)dq;
+        pp.y = (int)(uint32_t)c[CEV_PASS];
+    }
+    lv[cj >> 1] = pp;
+    if (nb != b0) lv[LN_BASE / 4] = make_int4((int)(uint32_t)nb, (int)(uint32_t)(nb >> 32), L[5].z, L[5].w);
+    lv[6] = make_int4((int)(uint32_t)o.occ_pass, (int)(uint32_t)o.occ_preq, (int)(uint32_t)c[CEV_WAITING],
+                      (int)(uint32_t)c[CEV_BLOCK]);
+    lv[7] = make_int4((int)(uint32_t)c[CEV_PASS_REQUEST], (int)(uint32_t)c[CEV_BLOCK_REQUEST],
+                      (int)(uint32_t)c[CEV_OCCUPIED_PASS], (int)(uint32_t)c[CEV_OCCUPIED_BLOCK]);
+    int4 *cg = reinterpret_cast<int4 *>(R.group(cj));
+    cg[0] = i4_of(c[CEV_WAITING], c[CEV_BLOCK]);
+    cg[1] = i4_of(c[CEV_PASS_REQUEST], c[CEV_BLOCK_REQUEST]);
+    cg[2] = i4_of(c[CEV_OCCUPIED_PASS], c[CEV_OCCUPIED_BLOCK]);
+    return true;
+}
+static_assert(LN_BASE == 20 && LN_THR == 22 && LN_OCC == 24 && LN_CACHE == 26,
+              "run_compact's pieces: 5 = (base word, threshold), 6 = (occupy counters, WAITING, BLOCK), 7 = the rest");
+
+// The wide form (any sampleCount): the 64-bit header, its pairs loaded one by one.
+template <class PrioBefore>
+__device__ __forceinline__ bool run_wide(const ClusterState &st, const SlotParam &P, const Rec &R, double thr_in,
+                                         bool hdr_thr, int64_t qbase, const RunIn &ri, PrioBefore prio_before,
+                                         RunOut &ro) {
+    // The bucket start stands in for the first request's time: with intervalInMs = sampleCount x
+    // windowLengthInMs every validity test gives the same answer for any time in the run's bucket.
+    const int32_t a = ri.a;
+    const int64_t q = qbase + ri.bd;  // bucket number
+    const int64_t ws = q * P.W;
+    const int64_t t0 = ws;
+    const int64_t qs = div_pos(q, P.S);
+    const int cj = (int)(q - qs * P.S);
+    const int jh = cj + 1 == P.S ? 0 : cj + 1;  // LeapArray.getValidHead index ((t0 + W) / W) % S
+    const int4 *v = reinterpret_cast<const int4 *>(R.r);
+    const int4 *hv = reinterpret_cast<const int4 *>(R.w_cache());
+    const int4 *ov = reinterpret_cast<const int4 *>(&R.w_occ());
+    const int4 o0 = ov[0], o1 = ov[1];
+    int4 c01 = hv[0], c23 = hv[1], c45 = hv[2];
+    const int4 meta = hv[3];  // (tag, threshold)
+    const int4 cur = v[cj];   // the current bucket's pair
+    const double thr = hdr_thr ? f64_hi(meta) : thr_in;
+    auto valid = [&](int64_t w) { return w != kAbsent && !(t0 - w > (int64_t)P.interval); };
+    int64_t bp = 0, hstart = kAbsent, hpass = 0;
+    for (int jj = 0; jj < P.S; ++jj) {
+        const int4 sp = v[jj];
+        const int64_t w = i64_lo(sp), pv = i64_hi(sp);
+        if (jj == jh) {
+            hstart = w;
+            hpass = pv;
+        }
+        if (jj != cj && valid(w)) bp += pv;
+    }
+    const int64_t old = i64_lo(cur);
+    if (a <= 0 || (old != kAbsent && ws < old)) return false;
+    if (ri.cp_tot > 0 && (P.S <= 1 || 1000 / P.S <= 0)) return false;
+    const bool rot = old == kAbsent || ws > old;
+    const bool tag_was_cur = i64_lo(meta) == old;
+    if (!rot && !tag_was_cur) {  // the current bucket's counters are not the cached group: the array
+        const int4 *cv = reinterpret_cast<const int4 *>(R.group(cj));
+        c01 = cv[0];
+        c23 = cv[1];
+        c45 = cv[2];
+    }
+    int64_t c[CEV_N];
+    SlotOcc o{i64_lo(o0), i64_hi(o0), o1.x, o1.y};
+    bool occ_dirty = false;
+    if (rot) {
+#pragma unroll
+        for (int k = 0; k < CEV_N; ++k) c[k] = 0;
+        if (old != kAbsent) occ_transfer(c, o, occ_dirty);
+    } else {
+        c[CEV_PASS] = i64_hi(cur);
+        c[CEV_WAITING] = i64_lo(c01);
+        c[CEV_BLOCK] = i64_hi(c01);
+        c[CEV_PASS_REQUEST] = i64_lo(c23);
+        c[CEV_BLOCK_REQUEST] = i64_hi(c23);
+        c[CEV_OCCUPIED_PASS] = i64_lo(c45);
+        c[CEV_OCCUPIED_BLOCK] = i64_hi(c45);
+    }
+    // getValidHead after the rotation (the head is the current bucket when S == 1)
+    const int64_t head = jh == cj ? c[CEV_PASS] : (valid(hstart) ? hpass : 0);
+    auto waiting_others = [&]() {
+        int64_t w0 = 0;
+#pragma nounroll
+        for (int jj = 0; jj < P.S; ++jj)
+            if (jj != cj && valid(R.w_start(jj))) w0 += R.cnt(CEV_WAITING, jj);
+        return w0;
+    };
+    run_decide(st, P, thr, ri, prio_before, waiting_others, bp, head, c, o, occ_dirty, ro);
+    // 16-byte stores: the (start, PASS) pair, the six other counters (one 48-byte group), the occupy state
+    const int64_t stv = rot ? ws : old;
+    reinterpret_cast<int4 *>(R.r)[cj] = i4_of(stv, c[CEV_PASS]);
+    c01 = i4_of(c[CEV_WAITING], c[CEV_BLOCK]);
+    c23 = i4_of(c[CEV_PASS_REQUEST], c[CEV_BLOCK_REQUEST]);
+    c45 = i4_of(c[CEV_OCCUPIED_PASS], c[CEV_OCCUPIED_BLOCK]);
+    int4 *cg = reinterpret_cast<int4 *>(R.group(cj));  // the array (authoritative)
+    cg[0] = c01;
+    cg[1] = c23;
+    cg[2] = c45;
+    // the header's cache is written when it must stay coherent (it already held this bucket); otherwise it
+    // is left alone -- its tag then names another bucket
+    if (!rot && tag_was_cur) {
+        int4 *ch = reinterpret_cast<int4 *>(R.w_cache());
+        ch[0] = c01;
+        ch[1] = c23;
+        ch[2] = c45;
+    }
+    if (occ_dirty) {
+        int4 *ow = reinterpret_cast<int4 *>(&R.w_occ());
+        ow[0] = i4_of(o.occ_pass, o.occ_preq);
+        ow[1] = make_int4(o.has_occ, o.pad, o1.z, o1.w);  // the spare word stored back unchanged
+    }
     return true;
 }
 
@@ -886,7 +941,7 @@ __global__ __launch_bounds__(kRunThreads) void k_results(BatchScratch sc, const 
 //               acquire count are written at its head position (run records indexed by position),
 //               prioritized positions are compacted into plist[h0 ..), rule heads into LDS.
 //   2 flows   : one lane per owned rule walks its runs in time order -- the closed form
-//               (run_fast) or the exact per-request replay (request_exact) -- and the rule's
+//               (run_compact / run_wide) or the exact per-request replay (request_exact) -- and the rule's
 //               request count feeds the next batch's hot-set candidates.
 //   3 results : the same scan again; every request reads its run's record and writes its
 //               TokenResult (runs replayed in step 2 wrote theirs already).
@@ -1318,11 +1373,9 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
     const uint32_t nfw = (dbg & 1) ? 0u : nf;
     uint32_t f = threadIdx.x, r = 0, r1 = 0, s = 0;
     SlotParam P;
-    Rec R{nullptr, 0};
+    Rec R{nullptr, 0, 0};
     double thr = 0;
     int64_t qbase = 0;
-    RecCarry<10> rc;
-    rc.have = false;
     const bool hdr_thr = st.uni_S && !simple;  // the closed form takes the threshold from the record header
     auto take_rule = [&]() {
         r = fheads[f];
@@ -1337,7 +1390,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         }
         if (st.uni_S) {
             // uniform geometry: the record address and the window geometry without the parameter
-            // load; the threshold is the record header's copy (Rec::thr), which comes with the
+            // load; the threshold is the record's copy (Rec::thr), which comes with the
             // header's loads (simple mode's threshold is a parameter load beside them)
             P.S = st.uni_S;
             P.W = st.uni_W;
@@ -1354,7 +1407,6 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         R = rec_of(st, P);
         thr = simple ? P.thr_simple : P.thr;
         qbase = div_pos(ts_base, P.W);
-        rc.have = false;
     };
     bool live = f < nfw;
     if (live) take_rule();
@@ -1396,16 +1448,11 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
             return lo;
         };
         RunOut ro;
-        // sampleCount <= 10 (the default, every C3 rule): ten pair registers carried between runs;
-        // larger sampleCounts load the pairs every run
-        bool fast;
-        if (P.S <= 10) {
-            fast = run_fast<decltype(prio_before), 10>(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro, rc);
-        } else {
-            RecCarry<0> rc0;
-            rc0.have = false;
-            fast = run_fast<decltype(prio_before), 0>(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro, rc0);
-        }
+        // a compact record (sampleCount <= 10 and nothing outgrew the line: every C3 rule) is decided from
+        // its one line; a wide one from the 64-bit header
+        bool wide;
+        bool fast = run_compact(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro, wide);
+        if (wide) fast = run_wide(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro);
         if (!fast) {
             for (uint32_t j = r; j < r + ri.n; ++j) {
                 const uint32_t i = el_idx(EL(j));
@@ -1414,7 +1461,6 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
                 out[i] = request_exact(st, s, t, in.acq_at(i), p, simple);
             }
             ro.mode = RUN_DONE;
-            rc.have = false;  // the record changed in memory
         }
         // a closed-form run's TokenResults: from its flows lane when it is short (or the long-run list is
         // full), else from a whole wave in the results phase (s_long)
@@ -2732,7 +2778,7 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const uint32_t *__restrict_
     return lo + (uint32_t)__popcll(__ballot(below));
 }
 
-// One wave per hot rule: its runs in bucket order, each with the closed form of run_fast (the S
+// One wave per hot rule: its runs in bucket order, each with the closed form of run_compact / run_wide (the S
 // window buckets are read by S lanes, the sums are wave reductions, the decisions are uniform
 // scalar arithmetic, lane 0 stores the bucket).
 // Hot run records, bucket-major: a bucket's runs of consecutive hot ids are adjacent, so
@@ -2809,8 +2855,9 @@ __global__ __launch_bounds__(kThreads) void k_hot_flows(ClusterState st, BatchSc
         const int64_t qs = div_pos(q, P.S);
         const int cj = (int)(q - qs * P.S);
         const int jh = cj + 1 == P.S ? 0 : cj + 1;
-        const int64_t w_ld = R.start(jl), pv_ld = R.cnt(CEV_PASS, jl);
-        const int64_t cl_ld = R.cnt(kl, cj);
+        // the record's form is the same for the whole wave (one rule), so the accessors' branch is uniform
+        const int64_t w_ld = R.start(jl), pv_ld = R.pass(jl);
+        const int64_t cl_ld = kl == CEV_PASS ? R.pass(cj) : R.cnt(kl, cj);
         const SlotOcc o_ld = R.occ();
         const uint32_t p0 = plo < phi ? wave_lower_bound(pr, plo, phi, j0, lane) : plo;
         const uint32_t p1 = plo < phi ? wave_lower_bound(pr, p0, phi, j0 + n, lane) : plo;
@@ -2877,14 +2924,19 @@ __global__ __launch_bounds__(kThreads) void k_hot_flows(ClusterState st, BatchSc
         if (lane == CEV_BLOCK) cl += (int64_t)nblk;
         if (lane == CEV_BLOCK_REQUEST) cl += nblk;
         if (lane == CEV_OCCUPIED_BLOCK) cl += (int64_t)(np_after - cw);
+        int64_t cg[kCacheWords];  // the six other counters in array order (WAITING first)
+#pragma unroll
+        for (int k = 0; k < kCacheWords; ++k) cg[k] = lane_i64(cl, k == 0 ? (int)CEV_WAITING : k);
         if (ok) {
-            if (lane < CEV_N) R.cnt(lane, cj) = cl;
-            // the header's cached group follows (the cold closed form reads it when the rule turns cold)
-            if (lane > 0 && lane < CEV_N) R.cache()[lane == CEV_WAITING ? 0 : lane] = cl;
+            if (lane > 0 && lane < CEV_N) R.cnt(lane, cj) = cl;
+            // lane 0 stores what depends on the record's form (a value that does not fit widens the record
+            // inside the accessor); the cached group follows (the cold closed form reads it when the rule
+            // turns cold)
             if (lane == 0) {
-                if (rot) R.start(cj) = ws;
-                if (occ_dirty) R.occ() = o;
-                R.tag() = ws;
+                if (rot) R.set_start(cj, ws);
+                R.set_pass(cj, cl);
+                if (occ_dirty) R.set_occ(o);
+                R.set_cache(cj, cg);
             }
         } else if (lane == 0) {
             atomicAdd(&sc.counters[CTL_HOTERR], 1u);
@@ -3533,20 +3585,23 @@ __global__ __launch_bounds__(kThreads) void k_cluster_nodes(ClusterState st, con
         cur_window(st, P, s, now);
         const Rec R = rec_of(st, P);
         int64_t sb = 0, sp = 0;
-        if (P.S <= 10) {  // unconditional loads (clamped index), issued together
-            int4 pr[10];
-            int64_t bl[10];
+        if (P.S <= kLnPairs && !R.wide()) {
+            // a compact record: starts and PASS from its one line, BLOCK from the array; unconditional loads
+            // (clamped index), issued together
+            int4 pr[kLnPairs / 2 + 1];
+            int64_t bl[kLnPairs];
 #pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const int jj = min(j, P.S - 1);
-                pr[j] = reinterpret_cast<const int4 *>(R.r)[jj];
-                bl[j] = R.cnt(CEV_BLOCK, jj);
-            }
+            for (int k = 0; k < kLnPairs / 2 + 1; ++k) pr[k] = reinterpret_cast<const int4 *>(R.ln())[k];
 #pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const int64_t w = i64_lo(pr[j]);
-                if (j < P.S && w != kAbsent && !(now - w > (int64_t)P.interval)) {
-                    sp += i64_hi(pr[j]);
+            for (int j = 0; j < kLnPairs; ++j) bl[j] = R.cnt(CEV_BLOCK, min(j, P.S - 1));
+            const int64_t base = ln_base((uint64_t)i64_lo(pr[LN_BASE / 4]));
+#pragma unroll
+            for (int j = 0; j < kLnPairs; ++j) {
+                const uint32_t d = (uint32_t)((j & 1) ? pr[j / 2].z : pr[j / 2].x);
+                const uint32_t pv = (uint32_t)((j & 1) ? pr[j / 2].w : pr[j / 2].y);
+                const int64_t w = ln_dec_bucket(d, base) * (int64_t)P.W;
+                if (j < P.S && d != kLnNoBucket && !(now - w > (int64_t)P.interval)) {
+                    sp += (int64_t)pv;
                     sb += bl[j];
                 }
             }
@@ -3584,14 +3639,7 @@ __global__ void k_init_slots(ClusterState st, const uint32_t *slots, uint32_t n)
     if (i >= n) return;
     const uint32_t s = slots[i];
     const SlotParam P = st.param[s];
-    const Rec R = rec_of(st, P);
-    for (int j = 0; j < P.S; ++j) {
-        R.start(j) = kAbsent;
-        bucket_zero(R, j);
-    }
-    R.occ() = SlotOcc{0, 0, 0, 0};
-    R.tag() = kAbsent;
-    R.thr() = P.thr;
+    rec_of(st, P).init(P.thr);
 }
 
 __global__ void k_rec_thr(ClusterState st, uint32_t n) {
@@ -3599,7 +3647,7 @@ __global__ void k_rec_thr(ClusterState st, uint32_t n) {
     if (s >= n) return;
     const SlotParam P = st.param[s];
     if (P.S <= 0) return;  // not allocated (its parameters are zero, its boff is no record)
-    rec_of(st, P).thr() = P.thr;
+    rec_of(st, P).set_thr(P.thr);
 }
 
 

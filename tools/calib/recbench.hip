@@ -1,15 +1,19 @@
 // Calibration of the cold-rule record access (k_cold_fused's flows phase) on this box.
-// 1M records of 768 B (the S = 10 layout: a 256-byte header of two 128-byte lines + the counter
+// 1M records of 768 B (the S = 10 layout before the decision line: a 256-byte header of two 128-byte lines + the counter
 // array), a list of `touched` distinct slots in ascending order (as a partition bin hands them to
 // its lanes).  Per touched rule: read the header, sum the ten (start, PASS) pairs, write one pair
-// and one 48-byte counter group (what run_fast stores).
+// and one 48-byte counter group (what the closed form of a run stores).
 //   lane   : one lane per rule, 16 int4 loads per lane (the current form)
 //   trans  : per wave 64 rules; each load instruction fetches 4 headers whole (16 lanes per header,
 //            8 full lines), LDS hands each lane its rule's 16 pieces (padded rows)
 //   coop   : 16 lanes per rule, one int4 each, DPP row reduction; the wave's 64 rules in 16 steps
 //            with all the loads issued first
 //   lane2  : one lane per rule, 2 int4 loads (load count scaling)
-// Usage: ./recbench [touched] [wg_threads]
+//   lane8  : one lane per rule over records of 896 B whose first 128-byte line holds the whole decision
+//            state in 32-bit fields: 8 int4 loads from that one line, one 16-byte piece stored back into
+//            it and one 48-byte counter group stored into the 64-bit array behind the full header
+// Usage: ./recbench [touched] [wg_threads] [rounds]
+// With rounds > 1 only lane, lane2 and lane8 are repeated, to learn their run-to-run spread.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -55,6 +59,27 @@ __global__ void k_lane2(int4 *rec, const uint32_t *__restrict__ sl, uint32_t n) 
     g[0] = b;
     g[1] = a;
     g[2] = b;
+}
+
+constexpr int kRec8I4 = 56;  // 896 B: the decision line, the 256-byte 64-bit header, the counter array
+constexpr int kLineI4 = 8;   // 128 B
+
+__global__ void k_lane8(int4 *rec, const uint32_t *__restrict__ sl, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int4 *r = rec + (size_t)sl[i] * kRec8I4;
+    int4 h[kLineI4];
+#pragma unroll
+    for (int k = 0; k < kLineI4; ++k) h[k] = r[k];
+    unsigned long long s = 0;  // ten (bucket delta, PASS) pairs of u32, two per int4
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s += (unsigned long long)(unsigned)h[k].y + (unsigned)h[k].w;
+    const int cj = h[5].x & 3;
+    r[cj] = make_int4(h[cj].x, (int)s, h[cj].z + 1, h[cj].w);
+    int4 *g = r + kLineI4 + kHdrI4 + 3 * cj;
+    g[0] = h[5];
+    g[1] = h[6];
+    g[2] = h[7];
 }
 
 // per wave: 64 rules; rows of 17 int4 (one pad) so a lane's 16 reads spread over the banks
@@ -179,9 +204,16 @@ int main(int argc, char **argv) {
     const uint32_t nslots = 1u << 20;
     const uint32_t touched = argc > 1 ? (uint32_t)atoi(argv[1]) : 700000u;
     const int wg = argc > 2 ? atoi(argv[2]) : 256;
-    int4 *rec; uint32_t *sl, *slr;
+    const int rounds = argc > 3 ? atoi(argv[3]) : 1;
+    if (touched == 0 || touched > nslots || wg < 64 || wg > 1024 || wg % 64 || rounds < 1) {
+        printf("usage: recbench [touched 1..%u] [wg_threads 64..1024, a multiple of 64] [rounds]\n", nslots);
+        return 2;
+    }
+    int4 *rec, *rec8; uint32_t *sl, *slr;
     CK(hipMalloc(&rec, (size_t)nslots * kRecI4 * 16));
     CK(hipMemset(rec, 0, (size_t)nslots * kRecI4 * 16));
+    CK(hipMalloc(&rec8, (size_t)nslots * kRec8I4 * 16));
+    CK(hipMemset(rec8, 0, (size_t)nslots * kRec8I4 * 16));
     std::vector<uint32_t> all(nslots);
     for (uint32_t k = 0; k < nslots; ++k) all[k] = k;
     uint64_t x = 0x9E3779B97F4A7C15ull;
@@ -194,10 +226,25 @@ int main(int argc, char **argv) {
     const uint32_t nb = (touched + wg - 1) / wg;
     const size_t lds = (size_t)(wg / 64) * 64 * 17 * 16;
     const double mb = touched * (256.0 + 64.0) / 1e6;  // header read + pair/group written (algorithmic)
+    const double mb8 = touched * (128.0 + 64.0) / 1e6;
+    for (int round = 1; round < rounds; ++round)
+        for (int order = 0; order < 2; ++order) {
+            const uint32_t *s = order ? slr : sl;
+            const char *on = order ? "random" : "sorted";
+            float t;
+            t = timeit([&] { hipLaunchKernelGGL(k_lane, dim3(nb), dim3(wg), 0, 0, rec, s, touched); });
+            printf("{\"mode\":\"lane\",\"order\":\"%s\",\"touched\":%u,\"wg\":%d,\"round\":%d,\"us\":%.2f,\"GBs\":%.1f}\n", on, touched, wg, round, t * 1e3, mb / t);
+            t = timeit([&] { hipLaunchKernelGGL(k_lane2, dim3(nb), dim3(wg), 0, 0, rec, s, touched); });
+            printf("{\"mode\":\"lane2\",\"order\":\"%s\",\"touched\":%u,\"wg\":%d,\"round\":%d,\"us\":%.2f,\"GBs\":%.1f}\n", on, touched, wg, round, t * 1e3, mb / t);
+            t = timeit([&] { hipLaunchKernelGGL(k_lane8, dim3(nb), dim3(wg), 0, 0, rec8, s, touched); });
+            printf("{\"mode\":\"lane8\",\"order\":\"%s\",\"touched\":%u,\"wg\":%d,\"round\":%d,\"us\":%.2f,\"GBs\":%.1f}\n", on, touched, wg, round, t * 1e3, mb8 / t);
+        }
     for (int order = 0; order < 2; ++order) {
         const uint32_t *s = order ? slr : sl;
         const char *on = order ? "random" : "sorted";
         float t;
+        t = timeit([&] { hipLaunchKernelGGL(k_lane8, dim3(nb), dim3(wg), 0, 0, rec8, s, touched); });
+        printf("{\"mode\":\"lane8\",\"order\":\"%s\",\"touched\":%u,\"wg\":%d,\"us\":%.2f,\"GBs\":%.1f}\n", on, touched, wg, t * 1e3, mb8 / t);
         t = timeit([&] { hipLaunchKernelGGL(k_lane, dim3(nb), dim3(wg), 0, 0, rec, s, touched); });
         printf("{\"mode\":\"lane\",\"order\":\"%s\",\"touched\":%u,\"wg\":%d,\"us\":%.2f,\"GBs\":%.1f}\n", on, touched, wg, t * 1e3, mb / t);
         t = timeit([&] { hipLaunchKernelGGL(k_ilv, dim3(nb), dim3(wg), 0, 0, rec, s, touched); });
