@@ -100,9 +100,9 @@ __global__ __launch_bounds__(kThreads) void k_classify(ClusterState st, const in
                                                        uint32_t n, int simple, uint32_t invalid_key,
                                                        uint64_t *__restrict__ el, uint64_t *__restrict__ out,
                                                        int hist_d, uint32_t ntiles, uint32_t *__restrict__ hist,
-                                                       int lb_npass, uint32_t *__restrict__ ghist) {
+                                                       int lb_npass, int lb_bits, uint32_t *__restrict__ ghist) {
     // hist_d > 0: this tile's histogram of the first digit (hist + scan sorts);
-    // lb_npass > 0: the global totals of every digit (look-back sorts)
+    // lb_npass > 0: the global totals of every digit of the lb_bits-wide key (look-back sorts)
     __shared__ uint32_t h[1024];
     const uint32_t nh = lb_npass > 0 ? (uint32_t)lb_npass << hist_d : (hist_d > 0 ? 1u << hist_d : 0u);
     if (nh) {
@@ -192,7 +192,8 @@ __global__ __launch_bounds__(kThreads) void k_classify(ClusterState st, const in
             if (lb_npass > 0) {
                 if (valid)
                     for (int p = 0; p < lb_npass; ++p)
-                        atomicAdd(&h[((uint32_t)p << hist_d) + ((key >> (p * hist_d)) & ((1u << hist_d) - 1))], 1u);
+                        atomicAdd(&h[((uint32_t)p << hist_d) +
+                                     ((key >> radix_pass_shift(p, hist_d, lb_bits)) & ((1u << hist_d) - 1))], 1u);
             } else if (hist_d > 0 && valid) {
                 atomicAdd(&h[key & ((1u << hist_d) - 1)], 1u);
             }
@@ -4909,7 +4910,7 @@ void cluster_decide_batch(const ClusterState &st, BatchScratch &sc, const int64_
     const uint64_t *el = sc.el[npass & 1];
     hipLaunchKernelGGL(cls, dim3(ntiles), dim3(kThreads), 0, s, st, flow_id, acquire, prio, ts_off, ts_base, n, simple,
                        invalid_key, sc.el[0], out, (limited || nofuse) ? 0 : d0, ntiles, sc.radix.hist,
-                       (lb && !limited) ? npass : 0, sc.radix.ghist);
+                       (lb && !limited) ? npass : 0, bits, sc.radix.ghist);
     if (!simple) apply_limiters(st.param, sc, sc.el[0], n, invalid_key, ts_base, ts_off, out, lims, nlims, s);
     const int np = radix_sort_u64(sc.el[0], sc.el[1], n, kSlotShift, bits, sc.radix, s, !limited && !nofuse);
     if (np != npass) throw HipError("radix pass count mismatch", __FILE__, __LINE__);

@@ -125,7 +125,7 @@ constexpr int kMaxPasses = 3;
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void k_rs_upfront(const uint32_t *__restrict__ keys, uint32_t n, int npass,
-                                                         uint32_t *__restrict__ ghist) {
+                                                         int bits, uint32_t *__restrict__ ghist) {
     constexpr int RADIX = 1 << D;
     __shared__ uint32_t h[kMaxPasses][RADIX];
     for (int d = threadIdx.x; d < kMaxPasses * RADIX; d += kThreads) (&h[0][0])[d] = 0;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void k_rs_upfront(const uint32_t *__restr
         const uint32_t e = base + r * kThreads + threadIdx.x;
         if (e < n) {
             const uint32_t k = keys[e];
-            for (int p = 0; p < npass; ++p) atomicAdd(&h[p][(k >> (p * D)) & (RADIX - 1)], 1u);
+            for (int p = 0; p < npass; ++p) atomicAdd(&h[p][(k >> radix_pass_shift(p, D, bits)) & (RADIX - 1)], 1u);
         }
     }
     __syncthreads();
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(kThreads) void k_rs64_hist(const uint64_t *__restri
 // Global digit totals of every pass in one read of the elements (look-back mode).
 template <int D>
 __global__ __launch_bounds__(kThreads) void k_rs64_upfront(const uint64_t *__restrict__ el, uint32_t n, int shift,
-                                                           int npass, uint32_t *__restrict__ ghist) {
+                                                           int npass, int bits, uint32_t *__restrict__ ghist) {
     constexpr int RADIX = 1 << D;
     __shared__ uint32_t h[kMaxPasses * RADIX];
     for (int d = threadIdx.x; d < kMaxPasses * RADIX; d += kThreads) h[d] = 0;
@@ -561,7 +561,8 @@ __global__ __launch_bounds__(kThreads) void k_rs64_upfront(const uint64_t *__res
         const uint32_t e = base + r * kThreads + threadIdx.x;
         if (e < n) {
             const uint64_t k = el[e];
-            for (int p = 0; p < npass; ++p) atomicAdd(&h[p * RADIX + ((uint32_t)(k >> (shift + p * D)) & (RADIX - 1))], 1u);
+            for (int p = 0; p < npass; ++p)
+                atomicAdd(&h[p * RADIX + ((uint32_t)(k >> (shift + radix_pass_shift(p, D, bits))) & (RADIX - 1))], 1u);
         }
     }
     __syncthreads();
@@ -921,20 +922,21 @@ static int radix_mode() {
 }
 
 template <int D>
-static void sort_passes(uint32_t *&ks, Payload *&ps, uint32_t *&kd, Payload *&pd, uint32_t n, int npass,
+static void sort_passes(uint32_t *&ks, Payload *&ps, uint32_t *&kd, Payload *&pd, uint32_t n, int npass, int bits,
                         RadixScratch &sc, hipStream_t s) {
     constexpr int RADIX = 1 << D;
     const uint32_t nt = (uint32_t)radix_tiles(n);
     const int mode = radix_mode();
     if (mode != 0) {
         for (int p = 0; p < npass; ++p) {
-            hipLaunchKernelGGL((k_rs_hist<D>), dim3(nt), dim3(kThreads), 0, s, ks, n, p * D, nt, sc.hist);
+            const int shift = radix_pass_shift(p, D, bits);
+            hipLaunchKernelGGL((k_rs_hist<D>), dim3(nt), dim3(kThreads), 0, s, ks, n, shift, nt, sc.hist);
             exclusive_scan_u32(sc.hist, sc.hist_scan, (size_t)RADIX * nt, sc.partial, s);
             if (mode == 1)
-                hipLaunchKernelGGL((k_rs_onesweep<D, false>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n, p * D,
+                hipLaunchKernelGGL((k_rs_onesweep<D, false>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n, shift,
                                    sc.hist_scan, nullptr, nullptr, kd, pd);
             else
-                hipLaunchKernelGGL((k_rs_scatter<D>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n, p * D, nt,
+                hipLaunchKernelGGL((k_rs_scatter<D>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n, shift, nt,
                                    sc.hist_scan, kd, pd);
             uint32_t *tk = ks; ks = kd; kd = tk;
             Payload *tp = ps; ps = pd; pd = tp;
@@ -945,12 +947,12 @@ static void sort_passes(uint32_t *&ks, Payload *&ps, uint32_t *&kd, Payload *&pd
     uint32_t *ghist = sc.hist_scan;                     // npass x RADIX digit totals -> bases
     uint32_t *ctr = sc.hist_scan + kMaxPasses * 2048;   // one tile counter per pass
     SGA_HIP_CHECK(hipMemsetAsync(ghist, 0, (kMaxPasses * 2048 + 64) * sizeof(uint32_t), s));
-    hipLaunchKernelGGL((k_rs_upfront<D>), dim3(nt), dim3(kThreads), 0, s, ks, n, npass, ghist);
+    hipLaunchKernelGGL((k_rs_upfront<D>), dim3(nt), dim3(kThreads), 0, s, ks, n, npass, bits, ghist);
     hipLaunchKernelGGL((k_rs_digit_base<D>), dim3(1), dim3(kThreads), 0, s, ghist, npass);
     for (int p = 0; p < npass; ++p) {
         SGA_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)nt * RADIX * sizeof(uint32_t), s));
-        hipLaunchKernelGGL((k_rs_onesweep<D, true>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n, p * D, ghist + p * RADIX,
-                           status, ctr + p, kd, pd);
+        hipLaunchKernelGGL((k_rs_onesweep<D, true>), dim3(nt), dim3(kThreads), 0, s, ks, ps, n,
+                           radix_pass_shift(p, D, bits), ghist + p * RADIX, status, ctr + p, kd, pd);
         uint32_t *tk = ks; ks = kd; kd = tk;
         Payload *tp = ps; ps = pd; pd = tp;
     }
@@ -959,29 +961,31 @@ static void sort_passes(uint32_t *&ks, Payload *&ps, uint32_t *&kd, Payload *&pd
 int radix_sort_pairs(uint32_t *keys, Payload *pay, uint32_t *keys_alt, Payload *pay_alt, size_t n, int bits,
                      RadixScratch &sc, hipStream_t s) {
     if (n == 0 || bits <= 0) return 0;
-    const int mb = max_digit_bits();
-    const int npass = (bits + mb - 1) / mb;
-    const int d = (bits + npass - 1) / npass;
+    const int d = radix_pairs_digit_bits(bits);
+    const int npass = (bits + d - 1) / d;
     if (npass > kMaxPasses) return -1;
     uint32_t *ks = keys, *kd = keys_alt;
     Payload *ps = pay, *pd = pay_alt;
     const uint32_t nn = (uint32_t)n;
     switch (d) {
-    case 1: sort_passes<1>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 2: sort_passes<2>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 3: sort_passes<3>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 4: sort_passes<4>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 5: sort_passes<5>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 6: sort_passes<6>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 7: sort_passes<7>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 8: sort_passes<8>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 9: sort_passes<9>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    case 10: sort_passes<10>(ks, ps, kd, pd, nn, npass, sc, s); break;
-    default: sort_passes<11>(ks, ps, kd, pd, nn, npass, sc, s); break;
+    case 1: sort_passes<1>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 2: sort_passes<2>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 3: sort_passes<3>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 4: sort_passes<4>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 5: sort_passes<5>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 6: sort_passes<6>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 7: sort_passes<7>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 8: sort_passes<8>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 9: sort_passes<9>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    case 10: sort_passes<10>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
+    default: sort_passes<11>(ks, ps, kd, pd, nn, npass, bits, sc, s); break;
     }
     return npass;  // result is in (keys, pay) if npass even, else in the alt buffers
 }
 
+
+// The pairs sort splits its key the same way.
+int radix_pairs_digit_bits(int bits) { return radix64_digit_bits(bits); }
 
 int radix64_digit_bits(int bits) {
     if (bits <= 0) return 1;
@@ -1001,7 +1005,7 @@ int radix64_lookback() {
 }
 
 template <int D>
-static int sort64_passes(uint64_t *a, uint64_t *alt, uint32_t n, int key_shift, int npass, RadixScratch &sc,
+static int sort64_passes(uint64_t *a, uint64_t *alt, uint32_t n, int key_shift, int npass, int bits, RadixScratch &sc,
                          hipStream_t s, bool hist0_ready, const uint64_t *first_src = nullptr,
                          const uint32_t *tile_n0 = nullptr, const uint32_t *dn = nullptr) {
     constexpr int RADIX = 1 << D;
@@ -1009,7 +1013,7 @@ static int sort64_passes(uint64_t *a, uint64_t *alt, uint32_t n, int key_shift, 
     if (first_src) {
         // pass 0 reads the producer's tile-compacted buffer, later passes alternate a <-> alt
         for (int p = 0; p < npass; ++p) {
-            const int shift = key_shift + p * D;
+            const int shift = key_shift + radix_pass_shift(p, D, bits);
             const uint64_t *src = p == 0 ? first_src : ((p & 1) ? a : alt);
             uint64_t *dst = (p & 1) ? alt : a;
             if (p > 0 || !hist0_ready)
@@ -1028,13 +1032,14 @@ static int sort64_passes(uint64_t *a, uint64_t *alt, uint32_t n, int key_shift, 
         if (!hist0_ready) {
             SGA_HIP_CHECK(hipMemsetAsync(sc.ghist, 0, kRadixGhistWords * sizeof(uint32_t), s));
             hipLaunchKernelGGL((k_rs64_upfront<D>), dim3(nt), dim3(kThreads), 0, s, src, n, key_shift, npass,
-                               sc.ghist);
+                               bits, sc.ghist);
         }
         hipLaunchKernelGGL((k_rs_digit_base<D>), dim3(1), dim3(kThreads), 0, s, sc.ghist, npass);
         for (int p = 0; p < npass; ++p) {
             SGA_HIP_CHECK(hipMemsetAsync(sc.hist, 0, (size_t)nt * RADIX * sizeof(uint32_t), s));
-            hipLaunchKernelGGL((k_rs64_sweep_lb<D>), dim3(nt), dim3(kThreads), 0, s, src, n, key_shift + p * D,
-                               sc.ghist + p * RADIX, sc.hist, sc.ghist + kMaxPasses * 2048 + p, sc.err, dst);
+            hipLaunchKernelGGL((k_rs64_sweep_lb<D>), dim3(nt), dim3(kThreads), 0, s, src, n,
+                               key_shift + radix_pass_shift(p, D, bits), sc.ghist + p * RADIX, sc.hist,
+                               sc.ghist + kMaxPasses * 2048 + p, sc.err, dst);
             uint64_t *t = src;
             src = dst;
             dst = t;
@@ -1042,7 +1047,7 @@ static int sort64_passes(uint64_t *a, uint64_t *alt, uint32_t n, int key_shift, 
         return npass;
     }
     for (int p = 0; p < npass; ++p) {
-        const int shift = key_shift + p * D;
+        const int shift = key_shift + radix_pass_shift(p, D, bits);
         if (p > 0 || !hist0_ready)
             hipLaunchKernelGGL((k_rs64_hist<D>), dim3(nt), dim3(kThreads), 0, s, src, n, shift, nt, sc.hist,
                                nullptr, nullptr);
@@ -1065,17 +1070,17 @@ int radix_sort_u64(uint64_t *a, uint64_t *alt, size_t n, int key_shift, int bits
     if (npass > kMaxPasses) return -1;
     const uint32_t nn = (uint32_t)n;
     switch (d) {
-    case 1: return sort64_passes<1>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 2: return sort64_passes<2>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 3: return sort64_passes<3>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 4: return sort64_passes<4>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 5: return sort64_passes<5>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 6: return sort64_passes<6>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 7: return sort64_passes<7>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 8: return sort64_passes<8>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 9: return sort64_passes<9>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    case 10: return sort64_passes<10>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
-    default: return sort64_passes<11>(a, alt, nn, key_shift, npass, sc, s, hist0_ready);
+    case 1: return sort64_passes<1>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 2: return sort64_passes<2>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 3: return sort64_passes<3>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 4: return sort64_passes<4>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 5: return sort64_passes<5>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 6: return sort64_passes<6>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 7: return sort64_passes<7>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 8: return sort64_passes<8>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 9: return sort64_passes<9>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    case 10: return sort64_passes<10>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
+    default: return sort64_passes<11>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready);
     }
 }
 
@@ -1092,17 +1097,17 @@ int radix_sort_u64_tiled(const uint64_t *src, const uint32_t *tile_n0, const uin
     if (npass > kMaxPasses) return -1;
     const uint32_t nn = (uint32_t)n;
     switch (d) {
-    case 1: return sort64_passes<1>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 2: return sort64_passes<2>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 3: return sort64_passes<3>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 4: return sort64_passes<4>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 5: return sort64_passes<5>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 6: return sort64_passes<6>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 7: return sort64_passes<7>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 8: return sort64_passes<8>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 9: return sort64_passes<9>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    case 10: return sort64_passes<10>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
-    default: return sort64_passes<11>(a, alt, nn, key_shift, npass, sc, s, hist0_ready, src, tile_n0, dn);
+    case 1: return sort64_passes<1>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 2: return sort64_passes<2>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 3: return sort64_passes<3>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 4: return sort64_passes<4>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 5: return sort64_passes<5>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 6: return sort64_passes<6>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 7: return sort64_passes<7>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 8: return sort64_passes<8>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 9: return sort64_passes<9>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    case 10: return sort64_passes<10>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
+    default: return sort64_passes<11>(a, alt, nn, key_shift, npass, bits, sc, s, hist0_ready, src, tile_n0, dn);
     }
 }
 

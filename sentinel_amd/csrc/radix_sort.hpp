@@ -23,7 +23,16 @@ struct RadixScratch {
     uint32_t *partial = nullptr;    // scan_partials_needed(hist entries)
 };
 
+// Bit offset, from the lowest bit of a `bits`-wide key field, of the digit that pass p of a sort with
+// d-bit digits ranks.  The last pass starts at bits - d: when d does not divide bits it overlaps the
+// pass before it instead of reaching past the field, so bits outside the field never move an element
+// (an LSD sort stays correct when a later digit repeats bits of an earlier one).
+__host__ __device__ inline int radix_pass_shift(int p, int d, int bits) { return p * d < bits - d ? p * d : bits - d; }
+
 size_t radix_tiles(size_t n);
+// Digit bits per pass of radix_sort_pairs for a `bits`-wide key; ceil(bits / digit) passes.
+// (Hidden: the shared libraries export nothing new for it.)
+__attribute__((visibility("hidden"))) int radix_pairs_digit_bits(int bits);
 size_t radix_hist_entries(size_t n, int bits);
 size_t scan_partials_needed(size_t n);
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *partial, hipStream_t s);
@@ -41,7 +50,8 @@ constexpr int kRadix64Tile = 4096;
 constexpr int kRadixMaxPasses = 3;
 constexpr size_t kRadixGhistWords = kRadixMaxPasses * 2048 + 64;
 // 1 when the u64 sort runs single-pass look-back sweeps (SGA_RADIX_MODE=0): the producer of the
-// elements then counts every pass's global digit totals into sc.ghist (zeroed first).
+// elements then counts every pass's global digit totals into sc.ghist (zeroed first); pass p's
+// digit starts at bit key_shift + radix_pass_shift(p, digit bits, bits).
 int radix64_lookback();
 int radix64_digit_bits(int bits);
 size_t radix64_tiles(size_t n);
