@@ -114,7 +114,7 @@ struct RAgg {
     uint32_t nh, flag, cnt;
 };
 
-// Per-run record of a hot rule (k_hot_flows), read per request by k_hot_final / k_prio_results.
+// Per-run record of a hot rule (k_hot_flows), read per request by k_hot_final_g / k_prio_results.
 // The first 32 bytes are all that a non-prioritized request needs.
 struct HotRun {
     int64_t s0;       // window PASS sum before the run
@@ -194,7 +194,6 @@ struct BatchScratch {
     uint8_t *run_bd;          // bucket delta of the run
     uint32_t *flow_first_run; // per rule touched in the batch: its first run
     uint32_t *plist;          // sorted positions of prioritized requests (ascending)
-    uint32_t *deferred;       // (flow, run) pairs handed from k_flows to k_flows_slow
     RunOut *run_out;
     RAgg *wave_carry;         // per 512-request wave slice: scan carry for k_results
     void *tile_agg;
@@ -232,9 +231,6 @@ struct BatchScratch {
     uint16_t *hpre;           // [kHotBuckets][kHot] the segment's hot requests before the bucket's first
     uint32_t *hbnd;           // [kHotBuckets] the bucket's first request
     HotRun *hrun;             // [kHotBuckets][kHot]
-    uint4 *hfin;              // [kHotBuckets][kHot]: (s0, f, start) of each hot run, what k_hot_final caches
-    uint2 *hfs;               // [kHotBuckets][kHot]: (f, start) of each hot run, what k_hot_final_p stages
-    double2 *hthr;            // [kHot] threshold and intervalInSecond of each hot rule (k_hot_flows)
     uint32_t *prank;          // per prioritized hot request (order of pel): its rank among its rule's requests
     uint32_t *plo, *phi;      // per hot id: its range in the prioritized region
     uint32_t *hot_tot;        // per hot id: requests in the batch
@@ -244,9 +240,6 @@ struct BatchScratch {
     unsigned long long *tmax_all;  // latest request time of every hot-path batch classified so far (precheck of
                                    // pipelined batches; shared by an engine's scratch sets)
     const uint64_t *el_sorted = nullptr, *pel_sorted = nullptr;  // stage 1's sorted cold / prioritized elements
-    bool hot_early = false;   // host: the batch's hot runs and results were queued in stage 1 (beside the cold sort)
-    bool sched2 = false;      // host: stream schedule 2 (cluster.hip hot_sched): the cold partition on `side`, the
-                              // hot results on `side2`; the cold stage waits for ev_fork
     uint32_t *hot_cand;       // [kHotCand] (slot, count) of cold rules with >= hot_min requests (hot_ctl[6])
     // cold partition: [segment][bin] counts (then in-group exclusive prefixes), [group][bin] group sums
     // (then prefixes), [bin] bin starts (+ the total); part_lb: slot bits below the bin (host, 0 = LSD sort)
@@ -256,11 +249,14 @@ struct BatchScratch {
     uint32_t small_max = 4096; // batches of at most this many requests take the one-workgroup path (sga_set_small_batch)
     int hot_lane_order = 0;   // lds_lane_order_ok() held on this device (set when the scratch is made)
     uint32_t hot_min = 64;    // smallest per-batch request count that makes a rule hot
-    // hot/cold overlap: after the sort the hot side (ranks, hot runs, hot results) runs on `side`
-    // beside the cold stage on the batch's stream (fork and join by events; made on first use)
+    // hot/cold overlap: the hot side (count scans, ranks, hot runs, hot results) runs on `side` beside the
+    // cold partition / sort and the cold stage on the batch's stream (made on first use).  ev_fork0: the key
+    // passes are done; ev_mid: the hot runs are done (the next hot set may start); ev_join: the hot results
+    // are done; ev_fork: a pipelined batch's stage 1 on `side` is done.
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork0 = nullptr, ev_mid = nullptr;
-    // the prioritized hot requests' sort on a stream of its own (beside the hot count scans on `side`)
+    // pipelined batches only: the prioritized hot requests' sort on a stream of its own (beside the hot count
+    // scans on `side`), joined by ev_prio
     hipStream_t side2 = nullptr;
     hipEvent_t ev_prio = nullptr;
 };
