@@ -60,6 +60,7 @@ extern "C" {
 #define SGA_ERANGE (-34)  /* batch larger than the configured capacity */
 #define SGA_ENOSYS (-38)  /* feature not available on this build */
 #define SGA_EAGAIN (-11)  /* sga_poll: the request is not decided yet */
+#define SGA_ENOENT (-2)   /* sga_query_origin_node: the (resource, origin) pair has no node yet */
 
 /* TokenResultStatus codes, CORE/cluster/TokenResultStatus.java:27-60 */
 #define SGA_TOKEN_BAD_REQUEST (-4)
@@ -383,6 +384,13 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
  * name table, like CtSph's chain map keys).  One ClusterNode per resource
  * (single default context, limitApp "default"; strategy DIRECT or RELATE:
  * FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116).
+ * Caller origins (ContextUtil.enter(name, origin)) are opt-in per engine: after
+ * sga_flow_set_origins, events submitted with an origin array (sga_submit_events_origin*)
+ * create and count one origin StatisticNode per (resource, origin) pair beside the
+ * ClusterNode (ClusterBuilderSlot.java:104-107, StatisticSlot.java:81-84, 101-104, 123-125,
+ * 160-161).  Every other call, and every engine that never registers origins, behaves as
+ * without them.  FlowRules limited to one origin or to "other" (sga_load_flow_rules_origin) read the origin
+ * node; a resource with such a rule is decided in arrival order by one lane, like a RELATE group.
  * ------------------------------------------------------------------------- */
 
 /* Coalescing queue of single local events (SphU.entry / Entry.exit from many application threads, one
@@ -587,6 +595,63 @@ int sga_submit_events_device(sga_engine *e, const uint8_t *d_kind, const uint32_
                              size_t n_values, int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream);
 int sga_events_device_status(sga_engine *e);
 int sga_query_node(sga_engine *e, uint32_t resource, int64_t now, sga_node_view *out);
+
+/* ---- caller origins (no struct changes: new entry points only) ---- */
+/* FlowRule.limitApp as an id: RuleConstant.LIMIT_APP_DEFAULT, a registered origin 1..n_origins,
+ * RuleConstant.LIMIT_APP_OTHER, or a name no event can carry */
+#define SGA_LIMIT_DEFAULT 0u
+#define SGA_LIMIT_OTHER 0xFFFFFFFEu
+#define SGA_LIMIT_UNKNOWN 0xFFFFFFFFu
+
+/* Registers the origins (after sga_flow_set_resources, once): dense ids 1..n_origins, the host keeps the
+ * names; 0 is the empty origin "".  max_origin_nodes sizes the device table of (resource, origin) node
+ * records (4,032 bytes each, initialised like a resource's node; the pair table beside it stays at most half
+ * full); 0 picks the default of 16,384 records (66 MB). */
+int sga_flow_set_origins(sga_engine *e, uint32_t n_origins, uint32_t max_origin_nodes);
+
+/* sga_load_flow_rules with a parallel limit_app[n] (SGA_LIMIT_*; NULL = all default, the old call).
+ * FlowRuleChecker.selectNodeByRequesterAndStrategy (FlowRuleChecker.java:136-166) for an entry of origin o: a
+ * rule with limit_app == o (o != 0) applies and its controller reads the pair's origin node (DIRECT) or
+ * ref_resource's ClusterNode (RELATE, the null rule included); a default rule behaves as ever; an "other" rule
+ * applies iff o != 0 and no rule of the resource names o (FlowRuleManager.isOtherOrigin,
+ * FlowRuleManager.java:137-153), and then reads like a matching rule; every other rule does not apply to the
+ * entry and no rater state is touched.  SGA_LIMIT_UNKNOWN, a name no event can carry, is valid and counted,
+ * never applies and names nobody for "other".  A cluster-mode rule asks the token service whatever its
+ * limit_app; only its local fallback selects a node.  Occupy and waiting counters go to the node the rule
+ * selected.  An id past n_origins that is neither constant: SGA_EINVAL.  Strategy 2 (CHAIN) stays invalid.
+ * A resource with a rule limited to an origin or to "other" is coupled through the ClusterNode its default
+ * rules read: its events are decided in arrival order by one lane, as a RELATE group of its own
+ * (sga_flow_group_of reports it).  This loader orders each resource's rules as FlowRuleComparator does
+ * (FlowRuleComparator.java:30-55, a stable sort by (cluster mode, limit_app == default): non-default first,
+ * cluster mode last), and a FLOW block detail is the index in that order; sga_load_flow_rules keeps the list
+ * order.  A reload resets the raters and keeps the origin nodes. */
+int sga_load_flow_rules_origin(sga_engine *e, const sga_flow_rule *rules, const uint32_t *limit_app, size_t n);
+
+/* sga_submit_events_ex / sga_submit_events_device with the caller's origin per event (origin[n], NULL = the
+ * old call).  Entries, exits, kind 2 and kind 3 events carry the origin of their entry, as they carry
+ * SGA_EV_INBOUND.  A kind 0 / 2 / 3 event with origin != 0 on a known resource creates the pair's origin node
+ * ahead of every check; the node then receives what the resource's node receives for the event: a pass adds a
+ * thread and PASS, SGA_PASS_WAIT a thread only, a block BLOCK; an exit adds rt and success, releases the
+ * thread and adds EXCEPTION on SGA_EV_ERROR; kind 2 adds BLOCK; kind 3 takes the pass and the thread back and
+ * adds BLOCK.  An exit of a pair without a node leaves origin nodes alone.  Decisions equal those of the
+ * same events without origins.  An id above n_origins refuses the whole call (SGA_EINVAL; device entry: the
+ * chunk, -1 for every event).  A chunk that would need more than max_origin_nodes records is refused
+ * before anything of it is applied (SGA_ENOMEM; device entry: through sga_events_device_status); the pairs it
+ * named keep the records it reserved, still without a node. */
+int sga_submit_events_origin(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
+                             const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
+                             const uint32_t *origin, size_t n, const uint64_t *param_values, size_t n_values,
+                             int8_t *decision, int32_t *wait_ms);
+int sga_submit_events_origin_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource,
+                                    int64_t ts_base, const uint32_t *d_ts_off, const int32_t *d_acquire,
+                                    const uint8_t *d_flags, const int64_t *d_rt, const uint64_t *d_param,
+                                    const uint32_t *d_origin, size_t n, const uint64_t *d_param_values,
+                                    size_t n_values, int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream);
+/* The origin node's view (ClusterNode.getOriginCountMap().get(origin)); SGA_ENOENT while the pair has none. */
+int sga_query_origin_node(sga_engine *e, uint32_t resource, uint32_t origin, int64_t now, sga_node_view *out);
+/* The origins with a node on the resource (the keys of getOriginCountMap), in no particular order: up to
+ * cap ids, *n = number written; SGA_ERANGE when there are more. */
+int sga_origin_nodes_of(sga_engine *e, uint32_t resource, uint32_t *origins, size_t cap, size_t *n);
 
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {

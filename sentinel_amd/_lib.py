@@ -62,6 +62,9 @@ class SgaFlowRule(C.Structure):
 
 
 SGA_REF_NONE = 0xFFFFFFFF  # a RELATE rule's refResource outside the engine; sga_flow_group_of: ungrouped
+# FlowRule.limitApp as sga_load_flow_rules_origin takes it (1..n_origins: a registered origin)
+SGA_LIMIT_DEFAULT, SGA_LIMIT_OTHER, SGA_LIMIT_UNKNOWN = 0, 0xFFFFFFFE, 0xFFFFFFFF
+SGA_ENOENT = -2  # sga_query_origin_node: the pair has no node yet
 
 
 class SgaParamRule(C.Structure):
@@ -185,6 +188,17 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]),
     "sga_query_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
+    "sga_flow_set_origins": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sga_load_flow_rules_origin": (C.c_int, [C.c_void_p, C.POINTER(SgaFlowRule), C.c_void_p, C.c_size_t]),
+    "sga_submit_events_origin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p]),
+    "sga_submit_events_origin_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "sga_query_origin_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
+    "sga_origin_nodes_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

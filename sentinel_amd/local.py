@@ -10,6 +10,8 @@ Same names and argument meaning as the Java API the engine replaces:
   SystemRuleManager.loadRules     CORE/slots/system/SystemRuleManager.java:114-300 (SystemSlot, inbound only)
   Constants.ENTRY_NODE            CORE/Constants.java:66 -> LocalSentinel.node(ENTRY_NODE), metrics rows
   ClusterNode statistics          CORE/node/StatisticNode.java:185-250 -> LocalSentinel.node
+  ContextUtil.enter(name, origin) CORE/context/ContextUtil.java:116-160 -> the `origin` of entry / submit
+  ClusterNode.getOriginCountMap   CORE/node/ClusterNode.java:116-118 -> LocalSentinel.origin_node / origin_nodes
 BlockException subclasses as in CORE/slots/block/BlockException.java and its subclasses.
 
 Every decision is computed by the HIP engine (libsentinel_amd.so).  The mocked
@@ -162,8 +164,9 @@ class Entry:
     """A passed entry; exit() records RT / success (StatisticSlot.exit) and breaker completion."""
 
     def __init__(self, owner: "LocalSentinel", rid: int, create_ts: int, count: int, param: Optional[int],
-                 wait_ms: int, inbound: bool = False, args=()):
+                 wait_ms: int, inbound: bool = False, args=(), origin: str = ""):
         self._owner = owner
+        self.origin = origin
         self.args = tuple(args)
         self.inbound = inbound
         self.rid = rid
@@ -186,27 +189,47 @@ class Entry:
         word = encode_args(self.args, pvals)
         fl = (EV_ERROR if self.error else 0) | EV_ARGS | (EV_INBOUND if self.inbound else 0)
         self._owner.submit([KIND_EXIT], [self.rid], [now], [self.count], [fl], [now - self.create_timestamp],
-                           [word], pvals)
+                           [word], pvals, origin=[self._owner.origin_id(self.origin)] if self.origin else None)
 
 
 class LocalSentinel:
     """The local slot chain (StatisticSlot, ParamFlowSlot, FlowSlot, DegradeSlot) on one engine."""
 
-    def __init__(self, engine: Engine, resources: Sequence[str]):
+    def __init__(self, engine: Engine, resources: Sequence[str], origins: Optional[Sequence[str]] = None,
+                 max_origin_nodes: int = 0):
+        """origins: the caller names events may carry (ContextUtil.enter's origin), registered up front like
+        the resources; None = no origin tracking.  max_origin_nodes sizes the engine's table of (resource,
+        origin) nodes (0: the engine's default)."""
         self.engine = engine
         self.resources: List[str] = list(resources)
         self.ids: Dict[str, int] = {r: i for i, r in enumerate(self.resources)}
         if len(self.ids) != len(self.resources):
             raise ValueError("duplicate resource names")
+        self.origins: List[str] = list(origins) if origins else []
+        # origin ids are 1-based: 0 is the empty origin
+        self.origin_ids: Dict[str, int] = {o: i + 1 for i, o in enumerate(self.origins)}
+        if len(self.origin_ids) != len(self.origins):
+            raise ValueError("duplicate origin names")
+        for o in self.origins:  # the names FlowRule.limitApp reserves (AuthorityRuleChecker / filterOrigin)
+            if o in (RuleConstant.LIMIT_APP_DEFAULT, RuleConstant.LIMIT_APP_OTHER) or not o:
+                raise ValueError(f"origin name {o!r} is reserved")
         check(_lib.load().sga_flow_set_resources(engine.handle, len(self.resources)), engine.handle, "setResources")
+        if self.origins:
+            check(_lib.load().sga_flow_set_origins(engine.handle, len(self.origins), max_origin_nodes),
+                  engine.handle, "setOrigins")
+
+    def origin_id(self, name: str) -> int:
+        """Dense id of a registered origin; "" is 0."""
+        return self.origin_ids[name] if name else 0
 
     def resource_id(self, name: str) -> int:
         return self.ids[name]
 
     # ---- batched form: the engine's native interface
-    def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None):
+    def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None):
         """Events in arrival order.  param_values: the values of Collection / array arguments
-        (events flagged SGA_EV_PARAM_LIST = 16 carry param = offset << 32 | count into it)."""
+        (events flagged SGA_EV_PARAM_LIST = 16 carry param = offset << 32 | count into it).
+        origin: each event's origin id (origin_id; 0 = none), on a sentinel with registered origins."""
         k = np.ascontiguousarray(kind, dtype=np.uint8)
         r = np.ascontiguousarray(resource, dtype=np.uint32)
         t = np.ascontiguousarray(ts, dtype=np.int64)
@@ -223,6 +246,18 @@ class LocalSentinel:
         dec = np.zeros(n, dtype=np.int8)
         wait = np.zeros(n, dtype=np.int32)
         vals = np.ascontiguousarray(param_values, dtype=np.uint64) if param_values is not None else None
+        if origin is not None:
+            og = np.ascontiguousarray(origin, dtype=np.uint32)
+            if len(og) != n:
+                raise ValueError("event arrays differ in length")
+            rc = _lib.load().sga_submit_events_origin(
+                self.engine.handle, k.ctypes.data, r.ctypes.data, t.ctypes.data, a.ctypes.data,
+                f.ctypes.data if f is not None else None, rtv.ctypes.data if rtv is not None else None,
+                pv.ctypes.data if pv is not None else None, og.ctypes.data, n,
+                vals.ctypes.data if vals is not None and len(vals) else None, len(vals) if vals is not None else 0,
+                dec.ctypes.data, wait.ctypes.data)
+            check(rc, self.engine.handle, "submitEvents")
+            return dec, wait
         rc = _lib.load().sga_submit_events_ex(
             self.engine.handle, k.ctypes.data, r.ctypes.data, t.ctypes.data, a.ctypes.data,
             f.ctypes.data if f is not None else None, rtv.ctypes.data if rtv is not None else None,
@@ -276,19 +311,20 @@ class LocalSentinel:
         return int(d.value), int(w.value)
 
     def submit_device(self, kind, resource, ts_base, ts_off, acquire, flags=None, rt=None, param=None,
-                      param_values=None, decision=None, wait=None, stream=None):
+                      param_values=None, decision=None, wait=None, stream=None, origin=None):
         """submit over device tensors (torch, on the engine's GPU), asynchronous on `stream` (torch stream or
         None = the engine stream): one chunk of at most max_batch events with timestamps ts_base + ts_off.
         Returns (decision int8, wait int32) device tensors; device_status() reports a chunk the device
         checks rejected (rc -EINVAL) or a full parameter map (rc -ENOMEM) as EngineError."""
         import torch
         n = kind.numel()
-        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param) if v is not None):
+        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param, origin) if v is not None):
             if x.numel() != n or not x.is_cuda or not x.is_contiguous():
                 raise ValueError("event tensors must be contiguous device tensors of one length")
         want = {"kind": (kind, torch.uint8), "resource": (resource, torch.int32), "ts_off": (ts_off, torch.int32),
                 "acquire": (acquire, torch.int32), "flags": (flags, torch.uint8), "rt": (rt, torch.int64),
-                "param": (param, torch.int64), "param_values": (param_values, torch.int64)}
+                "param": (param, torch.int64), "param_values": (param_values, torch.int64),
+                "origin": (origin, torch.int32)}
         for name, (x, dt) in want.items():
             if x is not None and x.element_size() != torch.empty(0, dtype=dt).element_size():
                 raise ValueError(f"{name}: element size of {dt} expected")
@@ -297,6 +333,14 @@ class LocalSentinel:
         if wait is None:
             wait = torch.empty(n, dtype=torch.int32, device=kind.device)
         ptr = (lambda x: x.data_ptr() if x is not None else None)
+        if origin is not None:  # origin ids per event (a full origin table: device_status, rc -ENOMEM)
+            rc = _lib.load().sga_submit_events_origin_device(
+                self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
+                acquire.data_ptr(), ptr(flags), ptr(rt), ptr(param), origin.data_ptr(), n, ptr(param_values),
+                param_values.numel() if param_values is not None else 0, decision.data_ptr(), wait.data_ptr(),
+                stream.cuda_stream if stream is not None else None)
+            check(rc, self.engine.handle, "submitEventsDevice")
+            return decision, wait
         rc = _lib.load().sga_submit_events_device(
             self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
             acquire.data_ptr(), ptr(flags), ptr(rt), ptr(param), n, ptr(param_values),
@@ -311,21 +355,23 @@ class LocalSentinel:
 
     # ---- SphU-style single entry
     def entry(self, resource: str, now: int, batch_count: int = 1, prioritized: bool = False, args=(),
-              entry_type: str = "OUT") -> Entry:
-        """SphU.entry(resource, entryType, batchCount, args); entry_type "IN" marks inbound traffic."""
+              entry_type: str = "OUT", origin: str = "") -> Entry:
+        """SphU.entry(resource, entryType, batchCount, args); entry_type "IN" marks inbound traffic; origin:
+        the caller the context was entered with (a registered origin name), kept by the Entry for its exit."""
         rid = self.ids[resource]
         inbound = entry_type == "IN"
         # the whole argument vector (SGA_EV_ARGS): ParamFlowSlot indexes args by each rule's paramIdx
         pvals: List[int] = []
         word = encode_args(tuple(args), pvals)
         fl = (EV_PRIORITIZED if prioritized else 0) | EV_ARGS | (EV_INBOUND if inbound else 0)
-        dec, wait = self.submit([KIND_ENTRY], [rid], [now], [batch_count], [fl], None, [word], pvals)
+        dec, wait = self.submit([KIND_ENTRY], [rid], [now], [batch_count], [fl], None, [word], pvals,
+                                origin=[self.origin_id(origin)] if origin else None)
         d = int(dec[0])
         if d in _EXC:
             raise _EXC[d](resource)
         param = param_value(args[0]) if len(args) > 0 and args[0] is not None and \
             not isinstance(args[0], (list, tuple)) else None
-        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args)
+        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin)
 
     def node(self, resource, now: int) -> NodeView:
         """ClusterNode views; resource ENTRY_NODE (or TOTAL_IN_RESOURCE_NAME) is Constants.ENTRY_NODE."""
@@ -335,6 +381,27 @@ class LocalSentinel:
         v = SgaNodeView()
         check(_lib.load().sga_query_node(self.engine.handle, rid, now, C.byref(v)), self.engine.handle, "node")
         return NodeView(*[getattr(v, f) for f, _ in SgaNodeView._fields_])
+
+    def origin_node(self, resource, origin, now: int) -> Optional[NodeView]:
+        """ClusterNode.getOriginCountMap().get(origin): the origin node's views, None while the resource has
+        not been entered from that origin."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        oid = origin if isinstance(origin, int) else self.origin_ids[origin]
+        v = SgaNodeView()
+        rc = _lib.load().sga_query_origin_node(self.engine.handle, rid, oid, now, C.byref(v))
+        if rc == _lib.SGA_ENOENT:
+            return None
+        check(rc, self.engine.handle, "originNode")
+        return NodeView(*[getattr(v, f) for f, _ in SgaNodeView._fields_])
+
+    def origin_nodes(self, resource) -> List[str]:
+        """The origins with a node on the resource (the keys of getOriginCountMap), sorted by id."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        buf = (C.c_uint32 * max(1, len(self.origins)))()
+        n = C.c_size_t()
+        check(_lib.load().sga_origin_nodes_of(self.engine.handle, rid, buf, len(self.origins), C.byref(n)),
+              self.engine.handle, "originNodes")
+        return [self.origins[i - 1] for i in sorted(buf[:n.value])]
 
     def metrics(self, now: int, cap: int = 1 << 16) -> List[MetricNode]:
         """MetricTimerListener.run (CORE/node/metric/MetricTimerListener.java:44-65): StatisticNode.metrics()
@@ -393,6 +460,11 @@ class FlowRuleManager:
         they fall back (fallbackToLocalWhenFail: the local rater, else pass)."""
         rules = [r for r in rules if r.resource in self.s.ids]
         arr = (SgaFlowRule * max(1, len(rules)))()
+        # a sentinel with registered origins names each rule's limitApp by id (sga_load_flow_rules_origin: the rule
+        # then applies to that origin's entries, or "other" to the origins no rule of the resource names, and
+        # reads the origin node); one without keeps the plain loader and its mapping
+        oids = getattr(self.s, "origin_ids", None) or None
+        lim = (C.c_uint32 * max(1, len(rules)))()
         for i, r in enumerate(rules):
             a = arr[i]
             a.resource = self.s.ids[r.resource]
@@ -401,11 +473,15 @@ class FlowRuleManager:
             a.control_behavior = r.control_behavior
             a.warm_up_period_sec = r.warm_up_period_sec
             a.max_queueing_time_ms = r.max_queueing_time_ms
-            # non-default limitApp and CHAIN are not served by the engine: rejected as invalid (the engine
-            # refuses strategy 2 itself).  RELATE (FlowRuleChecker.java:96-116) names its refResource by dense
+            # CHAIN is not served by the engine (it refuses strategy 2 itself), nor a non-default limitApp on a
+            # sentinel without registered origins: rejected as invalid.  RELATE (FlowRuleChecker.java:96-116) names its refResource by dense
             # id -- SGA_REF_NONE for a name this sentinel has no resource for: its ClusterNode never exists, so
             # the rule never blocks; a blank refResource is invalid (FlowRuleUtil.checkStrategyField)
-            a.strategy = r.strategy if r.limit_app == RuleConstant.LIMIT_APP_DEFAULT else -1
+            a.strategy = r.strategy if r.limit_app == RuleConstant.LIMIT_APP_DEFAULT or oids else -1
+            if oids:  # an unregistered name: no event can carry it (valid, never applies)
+                lim[i] = (_lib.SGA_LIMIT_DEFAULT if r.limit_app == RuleConstant.LIMIT_APP_DEFAULT else
+                          _lib.SGA_LIMIT_OTHER if r.limit_app == RuleConstant.LIMIT_APP_OTHER else
+                          oids.get(r.limit_app, _lib.SGA_LIMIT_UNKNOWN))
             if a.strategy == RuleConstant.STRATEGY_RELATE:
                 if r.ref_resource is None or not r.ref_resource.strip():
                     a.strategy = -1
@@ -419,6 +495,9 @@ class FlowRuleManager:
                 a.cluster_sample_count = 0 if cc is None else cc.sample_count
                 a.cluster_window_ms = 0 if cc is None else cc.window_interval_ms
                 a.cluster_strategy = 0 if cc is None else cc.strategy
+        if oids:
+            return check(_lib.load().sga_load_flow_rules_origin(self.s.engine.handle, arr, lim, len(rules)),
+                         self.s.engine.handle, "FlowRuleManager.loadRules")
         return check(_lib.load().sga_load_flow_rules(self.s.engine.handle, arr, len(rules)), self.s.engine.handle,
                      "FlowRuleManager.loadRules")
 

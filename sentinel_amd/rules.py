@@ -26,6 +26,7 @@ class RuleConstant:
     CONTROL_BEHAVIOR_RATE_LIMITER = 2
     CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER = 3
     LIMIT_APP_DEFAULT = "default"
+    LIMIT_APP_OTHER = "other"
 
 
 class ClusterRuleConstant:
