@@ -60,7 +60,7 @@ extern "C" {
 #define SGA_ERANGE (-34)  /* batch larger than the configured capacity */
 #define SGA_ENOSYS (-38)  /* feature not available on this build */
 #define SGA_EAGAIN (-11)  /* sga_poll: the request is not decided yet */
-#define SGA_ENOENT (-2)   /* sga_query_origin_node: the (resource, origin) pair has no node yet */
+#define SGA_ENOENT (-2)   /* sga_query_origin_node / sga_query_context_node: the pair has no node yet */
 
 /* TokenResultStatus codes, CORE/cluster/TokenResultStatus.java:27-60 */
 #define SGA_TOKEN_BAD_REQUEST (-4)
@@ -382,8 +382,8 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
 /* ---------------------------------------------------------------------------
  * Local path: resources are dense ids 0..n_resources-1 (the host keeps the
  * name table, like CtSph's chain map keys).  One ClusterNode per resource
- * (single default context, limitApp "default"; strategy DIRECT or RELATE:
- * FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116).
+ * (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116, 136-166: every limitApp,
+ * and strategy DIRECT, RELATE or CHAIN, each through the loader that knows it).
  * Caller origins (ContextUtil.enter(name, origin)) are opt-in per engine: after
  * sga_flow_set_origins, events submitted with an origin array (sga_submit_events_origin*)
  * create and count one origin StatisticNode per (resource, origin) pair beside the
@@ -391,6 +391,16 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
  * 160-161).  Every other call, and every engine that never registers origins, behaves as
  * without them.  FlowRules limited to one origin or to "other" (sga_load_flow_rules_origin) read the origin
  * node; a resource with such a rule is decided in arrival order by one lane, like a RELATE group.
+ * Contexts (the name of ContextUtil.enter(name, origin)) are opt-in the same way and independent of origins:
+ * after sga_flow_set_contexts, events submitted with a context array (sga_submit_events_ctx*) create and
+ * count one DefaultNode per (resource, context) pair (NodeSelectorSlot.java:158-177; DefaultNode's overrides
+ * count on it and on the ClusterNode), and a CHAIN rule (sga_load_flow_rules_ctx) reads the entry's
+ * DefaultNode when its refResource is the entry's context.  Context id 0 is "no tracked context" -- the
+ * default sentinel_default_context, whose DefaultNodes nobody reads: such an event creates and counts no
+ * context node (a deployment that wants a rule on the default context registers that name like any other).
+ * An entry under NullContext (past 2,000 context names, ContextUtil.trueEnter) skips the slot chain
+ * altogether: such entries are simply never submitted.  EntranceNodes and the invocation tree are not
+ * modelled: the engine does not see entry nesting.
  * ------------------------------------------------------------------------- */
 
 /* Coalescing queue of single local events (SphU.entry / Entry.exit from many application threads, one
@@ -478,7 +488,8 @@ typedef struct sga_flow_rule {
     int32_t control_behavior;      /* 0 default, 1 warm up, 2 rate limiter, 3 warm up + rate limiter */
     int32_t warm_up_period_sec;    /* default 10 */
     int32_t max_queueing_time_ms;  /* default 500 */
-    int32_t strategy;              /* STRATEGY_DIRECT 0 or STRATEGY_RELATE 1 (CHAIN 2 and negatives: invalid rule) */
+    int32_t strategy;              /* STRATEGY_DIRECT 0 or STRATEGY_RELATE 1; STRATEGY_CHAIN 2 through
+                                    * sga_load_flow_rules_ctx only (the other loaders: invalid rule, like negatives) */
     /* FlowRule.clusterMode (FlowRuleChecker.passClusterCheck, FlowRuleChecker.java:168-230): the
      * rule asks the token service; with the embedded server (sga_set_cluster_server) that is this
      * engine's cluster rules (sga_load_cluster_flow_rules, keyed by flowId) */
@@ -493,7 +504,7 @@ typedef struct sga_flow_rule {
      * rule passes untouched until the referenced resource has been entered once (its ClusterNode is null before:
      * FlowRuleChecker.java:86-89); an id >= n_resources (SGA_REF_NONE) names a resource that never is, so the
      * rule is valid, counted as loaded and never blocks.  A blank refResource is invalid (FlowRuleUtil.java:246-251):
-     * the caller passes strategy -1.  Ignored with DIRECT. */
+     * the caller passes strategy -1.  Ignored with DIRECT.  CHAIN (sga_load_flow_rules_ctx): the context id. */
     uint32_t ref_resource;
 } sga_flow_rule;
 
@@ -618,7 +629,7 @@ int sga_flow_set_origins(sga_engine *e, uint32_t n_origins, uint32_t max_origin_
  * entry and no rater state is touched.  SGA_LIMIT_UNKNOWN, a name no event can carry, is valid and counted,
  * never applies and names nobody for "other".  A cluster-mode rule asks the token service whatever its
  * limit_app; only its local fallback selects a node.  Occupy and waiting counters go to the node the rule
- * selected.  An id past n_origins that is neither constant: SGA_EINVAL.  Strategy 2 (CHAIN) stays invalid.
+ * selected.  An id past n_origins that is neither constant: SGA_EINVAL.  Strategy 2 (CHAIN) stays invalid here (sga_load_flow_rules_ctx).
  * A resource with a rule limited to an origin or to "other" is coupled through the ClusterNode its default
  * rules read: its events are decided in arrival order by one lane, as a RELATE group of its own
  * (sga_flow_group_of reports it).  This loader orders each resource's rules as FlowRuleComparator does
@@ -652,6 +663,55 @@ int sga_query_origin_node(sga_engine *e, uint32_t resource, uint32_t origin, int
 /* The origins with a node on the resource (the keys of getOriginCountMap), in no particular order: up to
  * cap ids, *n = number written; SGA_ERANGE when there are more. */
 int sga_origin_nodes_of(sga_engine *e, uint32_t resource, uint32_t *origins, size_t cap, size_t *n);
+
+/* ---- contexts (no struct changes: new entry points only) ---- */
+/* A CHAIN rule's refResource that is the name of no registered context: no event can carry it */
+#define SGA_CONTEXT_UNKNOWN 0xFFFFFFFFu
+
+/* Registers the contexts (after sga_flow_set_resources, once; independent of sga_flow_set_origins: an engine
+ * may register either, both or neither): dense ids 1..n_contexts, the host keeps the names; 0 is "no tracked
+ * context".  max_context_nodes sizes the device table of (resource, context) DefaultNode records, a second
+ * instance of the origin table (4,032 bytes a record); 0 picks the same default of 16,384 records (66 MB),
+ * a choice, not a measurement. */
+int sga_flow_set_contexts(sga_engine *e, uint32_t n_contexts, uint32_t max_context_nodes);
+
+/* sga_load_flow_rules_origin with strategy 2 (CHAIN) valid; limit_app NULL = every rule "default", legal on an
+ * engine without origins.  A CHAIN rule's ref_resource is its refResource as a context id: 1..n_contexts, or
+ * SGA_CONTEXT_UNKNOWN (valid, counted, keeps its place, never applies); 0 or any other id: invalid rule.
+ * FlowRuleChecker.selectNodeByRequesterAndStrategy / selectReferenceNode (FlowRuleChecker.java:96-116,
+ * 136-166): a CHAIN rule applies to an entry iff its limitApp test passes (the three-way test of
+ * sga_load_flow_rules_origin, so a CHAIN rule limited to an origin or to "other" is legal) and its
+ * refResource equals the entry's context; its controller then reads the entry's DefaultNode -- occupy and
+ * waiting counters go there only, DefaultNode forwards none of them.  Otherwise the rule does not apply and
+ * touches no rater state.  A cluster-mode CHAIN rule asks the token service; only its local fallback selects
+ * a node.  A resource with a CHAIN rule is decided in arrival order by one lane, as a group of its own
+ * (sga_flow_group_of reports it).  Rules are ordered as FlowRuleComparator does; a reload resets the raters and
+ * keeps the context nodes.  sga_load_flow_rules and sga_load_flow_rules_origin keep rejecting strategy 2. */
+int sga_load_flow_rules_ctx(sga_engine *e, const sga_flow_rule *rules, const uint32_t *limit_app, size_t n);
+
+/* The _origin entries with the entry's context per event (context[n]; either array may be NULL).  A kind 0 / 2 /
+ * 3 event with context != 0 on a known resource creates the pair's DefaultNode ahead of every check
+ * (NodeSelectorSlot.entry runs before ClusterBuilderSlot); the node then receives exactly what the origin node
+ * receives (above), so an event with an origin and a context counts on three nodes.  An exit creates nothing;
+ * an exit of a pair without a node -- one that arrives ahead of the pair's first entry in the same chunk
+ * included -- leaves context nodes alone.  ENTRY_NODE, breakers and parameter metrics know no context.
+ * Refusals are those of the origin entries: an id above n_contexts refuses the whole call or chunk
+ * (SGA_EINVAL), a full context table refuses it before anything is applied (SGA_ENOMEM), and the claims of
+ * both tables are taken back.  The sga_event_* queue and the JNI shim carry context 0, as they carry origin 0. */
+int sga_submit_events_ctx(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
+                          const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
+                          const uint32_t *origin, const uint32_t *context, size_t n, const uint64_t *param_values,
+                          size_t n_values, int8_t *decision, int32_t *wait_ms);
+int sga_submit_events_ctx_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base,
+                                 const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags,
+                                 const int64_t *d_rt, const uint64_t *d_param, const uint32_t *d_origin,
+                                 const uint32_t *d_context, size_t n, const uint64_t *d_param_values, size_t n_values,
+                                 int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream);
+/* The DefaultNode's view; SGA_ENOENT while the pair has none. */
+int sga_query_context_node(sga_engine *e, uint32_t resource, uint32_t context, int64_t now, sga_node_view *out);
+/* The contexts with a DefaultNode on the resource, in no particular order: up to cap ids, *n = number written;
+ * SGA_ERANGE when there are more. */
+int sga_context_nodes_of(sga_engine *e, uint32_t resource, uint32_t *contexts, size_t cap, size_t *n);
 
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {

@@ -65,6 +65,7 @@ SGA_REF_NONE = 0xFFFFFFFF  # a RELATE rule's refResource outside the engine; sga
 # FlowRule.limitApp as sga_load_flow_rules_origin takes it (1..n_origins: a registered origin)
 SGA_LIMIT_DEFAULT, SGA_LIMIT_OTHER, SGA_LIMIT_UNKNOWN = 0, 0xFFFFFFFE, 0xFFFFFFFF
 SGA_ENOENT = -2  # sga_query_origin_node: the pair has no node yet
+SGA_CONTEXT_UNKNOWN = 0xFFFFFFFF  # a CHAIN rule's refResource that is no registered context (sga_load_flow_rules_ctx)
 
 
 class SgaParamRule(C.Structure):
@@ -199,6 +200,17 @@ SIGNATURES = {
                                                   C.c_void_p]),
     "sga_query_origin_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
     "sga_origin_nodes_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sga_flow_set_contexts": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sga_load_flow_rules_ctx": (C.c_int, [C.c_void_p, C.POINTER(SgaFlowRule), C.c_void_p, C.c_size_t]),
+    "sga_submit_events_ctx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sga_submit_events_ctx_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "sga_query_context_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
+    "sga_context_nodes_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

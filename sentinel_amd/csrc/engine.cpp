@@ -2440,14 +2440,22 @@ int sga_submit_events_ex(sga_engine *e, const uint8_t *kind, const uint32_t *res
                          const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
                          size_t n, const uint64_t *param_values, size_t n_values, int8_t *decision,
                          int32_t *wait_ms) {
-    return sga_submit_events_origin(e, kind, resource, ts, acquire, flags, rt, param, nullptr, n, param_values,
-                                    n_values, decision, wait_ms);
+    return sga_submit_events_ctx(e, kind, resource, ts, acquire, flags, rt, param, nullptr, nullptr, n, param_values,
+                                 n_values, decision, wait_ms);
 }
 
 int sga_submit_events_origin(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
                              const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
                              const uint32_t *origin, size_t n, const uint64_t *param_values, size_t n_values,
                              int8_t *decision, int32_t *wait_ms) {
+    return sga_submit_events_ctx(e, kind, resource, ts, acquire, flags, rt, param, origin, nullptr, n, param_values,
+                                 n_values, decision, wait_ms);
+}
+
+int sga_submit_events_ctx(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
+                          const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
+                          const uint32_t *origin, const uint32_t *context, size_t n, const uint64_t *param_values,
+                          size_t n_values, int8_t *decision, int32_t *wait_ms) {
     if (n && (!kind || !resource || !ts || !acquire || !decision)) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
@@ -2471,7 +2479,7 @@ int sga_submit_events_origin(sga_engine *e, const uint8_t *kind, const uint32_t 
             }
         }
         return g.flow.submit(kind, resource, ts, acquire, flags, rt, param, n, decision, wait_ms, param_values,
-                             n_values, origin);
+                             n_values, origin, context);
     });
 }
 
@@ -2479,8 +2487,9 @@ int sga_submit_events_device(sga_engine *e, const uint8_t *d_kind, const uint32_
                              const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags,
                              const int64_t *d_rt, const uint64_t *d_param, size_t n, const uint64_t *d_param_values,
                              size_t n_values, int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream) {
-    return sga_submit_events_origin_device(e, d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param,
-                                           nullptr, n, d_param_values, n_values, d_decision, d_wait_ms, hip_stream);
+    return sga_submit_events_ctx_device(e, d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param,
+                                        nullptr, nullptr, n, d_param_values, n_values, d_decision, d_wait_ms,
+                                        hip_stream);
 }
 
 int sga_submit_events_origin_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource,
@@ -2488,6 +2497,16 @@ int sga_submit_events_origin_device(sga_engine *e, const uint8_t *d_kind, const 
                                     const uint8_t *d_flags, const int64_t *d_rt, const uint64_t *d_param,
                                     const uint32_t *d_origin, size_t n, const uint64_t *d_param_values,
                                     size_t n_values, int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream) {
+    return sga_submit_events_ctx_device(e, d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param,
+                                        d_origin, nullptr, n, d_param_values, n_values, d_decision, d_wait_ms,
+                                        hip_stream);
+}
+
+int sga_submit_events_ctx_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base,
+                                 const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags,
+                                 const int64_t *d_rt, const uint64_t *d_param, const uint32_t *d_origin,
+                                 const uint32_t *d_context, size_t n, const uint64_t *d_param_values, size_t n_values,
+                                 int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream) {
     if (n && (!d_kind || !d_resource || !d_ts_off || !d_acquire || !d_decision)) return SGA_EINVAL;
     if (ts_base < 0) return SGA_EINVAL;  // LeapArray.currentWindow(t < 0) returns null
     return guarded(e, [&](Engine &g) {
@@ -2517,7 +2536,8 @@ int sga_submit_events_origin_device(sga_engine *e, const uint8_t *d_kind, const 
         if (const int rc = g.flow.ensure_maps(n + n_values)) return rc;
         hipStream_t s = g.enter_stream(hip_stream);
         const int rc = g.flow.submit_device(d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param, n,
-                                            d_param_values, n_values, d_decision, d_wait_ms, s, d_origin);
+                                            d_param_values, n_values, d_decision, d_wait_ms, s, d_origin,
+                                            d_context);
         g.leave_stream(s);
         return rc;
     });
@@ -2540,7 +2560,7 @@ int sga_query_node(sga_engine *e, uint32_t resource, int64_t now, sga_node_view 
 int sga_flow_set_origins(sga_engine *e, uint32_t n_origins, uint32_t max_origin_nodes) {
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
-        return g.flow.set_origins(n_origins, max_origin_nodes);
+        return g.flow.set_pairs(sga::kPairOrigin, n_origins, max_origin_nodes);
     });
 }
 
@@ -2555,14 +2575,43 @@ int sga_load_flow_rules_origin(sga_engine *e, const sga_flow_rule *rules, const 
 int sga_query_origin_node(sga_engine *e, uint32_t resource, uint32_t origin, int64_t now, sga_node_view *out) {
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
-        return g.flow.query_origin(resource, origin, now, out);
+        return g.flow.query_pair(sga::kPairOrigin, resource, origin, now, out);
     });
 }
 
 int sga_origin_nodes_of(sga_engine *e, uint32_t resource, uint32_t *origins, size_t cap, size_t *n) {
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
-        return g.flow.origin_nodes_of(resource, origins, cap, n);
+        return g.flow.pair_nodes_of(sga::kPairOrigin, resource, origins, cap, n);
+    });
+}
+
+int sga_flow_set_contexts(sga_engine *e, uint32_t n_contexts, uint32_t max_context_nodes) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.set_pairs(sga::kPairContext, n_contexts, max_context_nodes);
+    });
+}
+
+int sga_load_flow_rules_ctx(sga_engine *e, const sga_flow_rule *rules, const uint32_t *limit_app, size_t n) {
+    if (n && !rules) return SGA_EINVAL;
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.load_flow_rules(rules, n, limit_app, true);
+    });
+}
+
+int sga_query_context_node(sga_engine *e, uint32_t resource, uint32_t context, int64_t now, sga_node_view *out) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.query_pair(sga::kPairContext, resource, context, now, out);
+    });
+}
+
+int sga_context_nodes_of(sga_engine *e, uint32_t resource, uint32_t *contexts, size_t cap, size_t *n) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.pair_nodes_of(sga::kPairContext, resource, contexts, cap, n);
     });
 }
 

@@ -873,31 +873,32 @@ __device__ bool param_local_check(const Ctx &c, uint32_t r, ParamRuleDev &p, int
     return true;
 }
 
-// ------------------------------------------------------------------ origin nodes: table and per-event adds
-__device__ __forceinline__ unsigned long long origin_key(uint32_t r, uint32_t o) {
+// ------------------------------------------------------------------ pair nodes (origin nodes, context
+// DefaultNodes): table and per-event adds
+__device__ __forceinline__ unsigned long long pair_key(uint32_t r, uint32_t o) {
     return ((unsigned long long)(r + 1u) << 32) | o;
 }
-__device__ __forceinline__ uint32_t origin_home(const OriginState &os, unsigned long long k) {
+__device__ __forceinline__ uint32_t pair_home(const PairState &os, unsigned long long k) {
     return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32) & os.mask;
 }
-// the pair's table slot, or kOriginNone (read only: after the chunk's claim pass)
-__device__ uint32_t origin_find(const OriginState &os, unsigned long long k) {
-    uint32_t h = origin_home(os, k);
+// the pair's table slot, or kPairNone (read only: after the chunk's claim pass)
+__device__ uint32_t pair_find(const PairState &os, unsigned long long k) {
+    uint32_t h = pair_home(os, k);
     for (uint32_t step = 0; step <= os.mask; ++step, h = (h + 1) & os.mask) {
         const unsigned long long cur = os.key[h];
         if (cur == k) return h;
-        if (cur == 0) return kOriginNone;
+        if (cur == 0) return kPairNone;
     }
-    return kOriginNone;
+    return kPairNone;
 }
 
 // the event's node record: its pair's, when the pair was created by this event or an earlier one (an exit
-// creates nothing: an exit of a pair never entered leaves origin nodes alone)
-__device__ __forceinline__ uint32_t origin_node_of(const OriginState &os, uint32_t i, uint8_t kd, uint32_t r, uint32_t o,
-                                                   uint32_t nres, uint64_t seq_base, const uint32_t *oslot) {
-    if (!o || r >= nres) return kOriginNone;
-    const uint32_t h = kd == SGA_KIND_EXIT ? origin_find(os, origin_key(r, o)) : oslot[i];
-    if (h == kOriginNone || os.born[h] > seq_base + i) return kOriginNone;
+// creates nothing: an exit of a pair never entered leaves the pair's nodes alone)
+__device__ __forceinline__ uint32_t pair_node_of(const PairState &os, uint32_t i, uint8_t kd, uint32_t r, uint32_t o,
+                                                 uint32_t nres, uint64_t seq_base, const uint32_t *oslot) {
+    if (!o || r >= nres) return kPairNone;
+    const uint32_t h = kd == SGA_KIND_EXIT ? pair_find(os, pair_key(r, o)) : oslot[i];
+    if (h == kPairNone || os.born[h] > seq_base + i) return kPairNone;
     return os.idx[h];
 }
 
@@ -919,7 +920,7 @@ __device__ __forceinline__ Payload origin_pack(uint32_t i, const uint8_t *__rest
     return Payload{i, ts_off[i], (uint32_t)acquire[i] & 0x7FFFFFFFu, code};
 }
 
-// StatisticSlot's adds of one event on its origin node: what the resource's node receives for it (chain_entry /
+// StatisticSlot's adds of one event on its origin node or its context's DefaultNode: what the resource's node receives for it (chain_entry /
 // chain_exit / blocked_event / revoke_event)
 __device__ __forceinline__ void origin_event(const Ctx &c, int64_t *node, const Payload &q, int64_t ts_base,
                                              const int64_t *__restrict__ rt_in) {
@@ -949,12 +950,37 @@ __device__ __forceinline__ void origin_event(const Ctx &c, int64_t *node, const 
     }
 }
 
-// An origin-ruled resource's entry (chain_entry<., true>): the event's origin, its origin node (null for origin
-// 0), and the limitApp of each of the resource's rules
+// The origin node and the DefaultNode of one event of a pair-ruled resource (null: the event carries no such id,
+// or its pair has no node), with the ids
+struct PairNodes {
+    int64_t *n[kPairKinds];
+    uint32_t id[kPairKinds];
+};
+__device__ __forceinline__ PairNodes pair_nodes_of(const PairCtx &pc, uint32_t i, uint8_t kd, uint32_t r, uint32_t nres) {
+    PairNodes pn{{nullptr, nullptr}, {0, 0}};
+#pragma unroll
+    for (int k = 0; k < kPairKinds; ++k) {
+        if (!pc.id[k]) continue;
+        pn.id[k] = pc.id[k][i];
+        const uint32_t rec = pair_node_of(pc.pt.t[k], i, kd, r, pn.id[k], nres, pc.seq_base, pc.slot[k]);
+        if (rec != kPairNone) pn.n[k] = pc.pt.t[k].node + (size_t)rec * kNodeWords;
+    }
+    return pn;
+}
+// StatisticSlot's adds of the event on both
+__device__ __forceinline__ void pair_count(const Ctx &c, const PairNodes &pn, const Payload &q, int64_t ts_base,
+                                           const int64_t *__restrict__ rt_in) {
+#pragma unroll
+    for (int k = 0; k < kPairKinds; ++k)
+        if (pn.n[k]) origin_event(c, pn.n[k], q, ts_base, rt_in);
+}
+
+// A pair-ruled resource's entry (chain_entry<., true>): the event's origin and context with their nodes (null for
+// id 0), the limitApp of each of the resource's rules and each rule's CHAIN context (0: the rule is not CHAIN)
 struct OriginSel {
-    int64_t *onode;
-    uint32_t origin;
+    const PairNodes *pn;
     const uint32_t *lim;
+    const uint32_t *cref;
 };
 
 template <bool kLru = false, bool kOrigin = false>
@@ -1039,14 +1065,21 @@ __device__ int8_t chain_entry(const Ctx &c, uint32_t r, const ResMem &m, int64_t
             // below); any other non-default rule selects no node for this entry: it passes, no rater state touched
             const uint32_t lim = osel->lim[k];
             if (lim != SGA_LIMIT_DEFAULT) {
-                const uint32_t o = osel->origin;
+                const uint32_t o = osel->pn->id[kPairOrigin];
                 bool applies = o != 0 && lim == o;
                 if (!applies && o != 0 && lim == SGA_LIMIT_OTHER) {
                     applies = true;
                     for (uint32_t j = 0; j < R.n_rules; ++j) applies = applies && osel->lim[j] != o;
                 }
-                if (!applies || !osel->onode) continue;
-                sel = osel->onode;
+                if (!applies || !osel->pn->n[kPairOrigin]) continue;
+                sel = osel->pn->n[kPairOrigin];
+            }
+            // selectReferenceNode (FlowRuleChecker.java:96-116), strategy CHAIN, once the limitApp test above has
+            // passed: the rule applies iff its refResource is the entry's context name, and then reads the
+            // entry's DefaultNode (occupy and waiting counters included: DefaultNode forwards none of those)
+            if (const uint32_t cr = osel->cref[k]) {
+                if (cr != osel->pn->id[kPairContext] || !osel->pn->n[kPairContext]) continue;
+                sel = osel->pn->n[kPairContext];
             }
         }
         if (fr.rel) {
@@ -1198,8 +1231,8 @@ __device__ __forceinline__ void entry_node_after_exit(const Ctx &c, int64_t t, i
 // inbound events, kGateBad on invalid input (the chunk is not applied).  A null gate (host entry)
 // lets every kernel run; the host launches only the ones the chunk needs.
 constexpr uint32_t kGateSeq = 1, kGateIn = 2, kGateBad = 4;
-// with kGateBad, set by the origin claim pass: the origin table filled (device_status: SGA_ENOMEM) / an origin id
-// past the registered ones (SGA_EINVAL, which wins as on the host entry)
+// with kGateBad, set by the pair-node claim pass: the origin or the context table filled (device_status:
+// SGA_ENOMEM) / an origin or context id past the registered ones (SGA_EINVAL, which wins as on the host entry)
 constexpr uint32_t kGateFull = 8, kGateOrigin = 16;
 __device__ __forceinline__ bool gate_is(const uint32_t *g, uint32_t mask, uint32_t want) {
     return !g || (*g & mask) == want;
@@ -1280,28 +1313,24 @@ __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *
         } else if (hp && (fl & SGA_EV_PARAM_LIST) && pvals) {
             pa = PArgs{pvals + (param_in[i] >> 32), (uint32_t)param_in[i]};
         }
-        // an origin-ruled resource (OriginCtx): its rules select their node by the event's origin, and its origin
-        // node is counted here, in arrival order (the statistics pass leaves such resources alone)
-        const OriginCtx *oc = st.octx;
-        int64_t *onode = nullptr;
-        uint32_t org = 0;
+        // a pair-ruled resource (PairCtx): its rules select their node by the event's origin and context, and its
+        // origin node and DefaultNode are counted here, in arrival order (the statistics pass leaves such
+        // resources alone)
+        const PairCtx *oc = st.octx;
+        PairNodes pn{{nullptr, nullptr}, {0, 0}};
         const bool oruled = oc && oc->oruled[r];
-        if (oruled) {
-            org = oc->origin ? oc->origin[i] : 0;
-            const uint32_t rec = origin_node_of(oc->os, i, kind[i], r, org, st.nres, oc->seq_base, oc->oslot);
-            if (rec != kOriginNone) onode = oc->os.node + (size_t)rec * kNodeWords;
-        }
+        if (oruled) pn = pair_nodes_of(*oc, i, kind[i], r, st.nres);
         if (kind[i] == 1) {
             chain_exit<true>(c, r, t, rt_in[i], a, (fl & SGA_EV_ERROR) != 0, hp, param_in[i], pa, i);
             if (in) entry_node_after_exit(c, t, rt_in[i], a, (fl & SGA_EV_ERROR) != 0);
-            if (onode) origin_event(c, onode, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
+            if (oruled) pair_count(c, pn, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
             continue;
         }
         st.node[(size_t)r * kNodeWords + kNodeEntered] = 1;  // ClusterBuilderSlot.entry: ahead of every check
         if (kind[i] == SGA_KIND_BLOCKED) {  // StatisticSlot's BlockException branch for a block thrown outside the engine
             blocked_event(c, r, t, a);
             if (in) node_add(c, entry_node(c), t, MB_BLOCK, a);
-            if (onode) origin_event(c, onode, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
+            if (oruled) pair_count(c, pn, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
             continue;
         }
         if (kind[i] == SGA_KIND_REVOKE) {
@@ -1312,7 +1341,7 @@ __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *
                 node_add(c, e, t, MB_PASS, -(int64_t)a);
                 node_add(c, e, t, MB_BLOCK, a);
             }
-            if (onode) origin_event(c, onode, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
+            if (oruled) pair_count(c, pn, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
             continue;
         }
         int8_t d;
@@ -1322,7 +1351,7 @@ __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *
             d = D_BLOCK_SYSTEM;
             w = sb;  // block detail: the SystemRule check
         } else if (oruled) {
-            const OriginSel os{onode, org, oc->rule_lim + st.res[r].rule_off};
+            const OriginSel os{&pn, oc->rule_lim + st.res[r].rule_off, oc->rule_ctx + st.res[r].rule_off};
             d = chain_entry<true, true>(c, r, res_global(c, r, st.res[r]), t, a, (fl & SGA_EV_PRIORITIZED) != 0, hp,
                                         param_in[i], &w, pa, i, &os);
         } else {
@@ -1331,7 +1360,7 @@ __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *
         if (in) entry_node_after_entry(c, t, a, d);
         decision[i] = d;
         wait_ms[i] = (int32_t)w;
-        if (onode) origin_event(c, onode, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
+        if (oruled) pair_count(c, pn, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base, rt_in);
     }
 }
 
@@ -1455,14 +1484,18 @@ __global__ __launch_bounds__(kEnTile) void k_entry_stats(FlowState st, int64_t m
     }
 }
 
-// ------------------------------------------------------------------ origin nodes
+// ------------------------------------------------------------------ pair nodes: origin nodes and DefaultNodes
 // The origin's StatisticNode of ClusterBuilderSlot.entry (ClusterBuilderSlot.java:104-107: created ahead of every
 // check, at the first entry of the resource from that origin) and StatisticSlot's adds on it
 // (context.getCurEntry().getOriginNode(): StatisticSlot.java:81-84 pass, :101-104 PriorityWaitException,
-// :123-125 BlockException, :160-161 exit).  No rule of the loaded kind reads an origin node, so decisions do not
+// :123-125 BlockException, :160-161 exit); the context's DefaultNode of NodeSelectorSlot.entry
+// (NodeSelectorSlot.java:158-177: created at the first entry of the resource in that context, ahead of
+// ClusterBuilderSlot) and the same adds on it (StatisticSlot counts on the DefaultNode, whose overrides forward to
+// the ClusterNode).  No rule of a resource that is not pair-ruled reads either, so its decisions do not
 // depend on them: a chunk's claim pass (k_oclaim) runs ahead of the checks, and its statistics pass applies the
 // finished decisions per node in arrival order (k_oelems, a stable sort by node, k_oshort / k_olong; small
-// chunks: k_oseq).
+// chunks: k_oseq).  One set of kernels serves both kinds: each takes both tables (PairTabs) and the chunk's id
+// arrays, either of which may be null.
 // a node's events of a chunk: one lane below this many, one workgroup in tiles from it (a choice, not measured:
 // a wave's lanes then loop over at most 63 events each, about what a workgroup's tile setup costs)
 #ifndef SGA_ORIGIN_LONG
@@ -1471,71 +1504,89 @@ __global__ __launch_bounds__(kEnTile) void k_entry_stats(FlowState st, int64_t m
 constexpr uint32_t kOriginLong = SGA_ORIGIN_LONG;
 constexpr int kOriginT = 256, kOriginTile = 1024;
 
-// Claim pass: every kind 0 / 2 / 3 event with an origin finds or claims its pair's slot (the CAS pattern of
+// The chunk's id arrays and claimed slots, one of each per kind of pair (a null id array: no event carries one)
+struct PairIds {
+    const uint32_t *id[kPairKinds];
+    uint32_t *slot[kPairKinds];
+};
+
+// Claim pass: every kind 0 / 2 / 3 event with an id finds or claims its pair's slot (the CAS pattern of
 // ptab_get) and lowers the pair's birth to its own sequence; the slot's winner takes the next node record.  A
-// full table or an origin id past n_origins refuses the chunk (ctl[1]; device entry: the gate).
-__global__ __launch_bounds__(kT) void k_oclaim(OriginState os, const uint8_t *__restrict__ kind,
-                                               const uint32_t *__restrict__ resource,
-                                               const uint32_t *__restrict__ origin, uint32_t n, uint32_t nres,
-                                               uint64_t seq_base, uint32_t *oslot, uint32_t *gate) {
+// full table or an id past n_ids refuses the chunk (ctl[0]; device entry: the gate).
+__global__ __launch_bounds__(kT) void k_oclaim(PairTabs pt, PairIds ids, const uint8_t *__restrict__ kind,
+                                               const uint32_t *__restrict__ resource, uint32_t n, uint32_t nres,
+                                               uint64_t seq_base, uint32_t *gate) {
     const uint32_t i = blockIdx.x * kT + threadIdx.x;
     uint32_t bad = 0;
     // a chunk k_lgate already refused claims nothing (this pass's own refusals carry kGateFull or kGateOrigin)
     if (gate && (*gate & kGateBad) && !(*gate & (kGateFull | kGateOrigin))) return;
     if (i < n) {
-        const uint32_t o = origin[i], r = resource[i];
-        uint32_t slot = kOriginNone;
-        if (o > os.n_origins) {
-            bad = kOriginBadId;
-        } else if (o && r < nres && kind[i] != SGA_KIND_EXIT) {
-            const unsigned long long k = origin_key(r, o);
-            uint32_t h = origin_home(os, k);
-            for (uint32_t step = 0; step <= os.mask; ++step, h = (h + 1) & os.mask) {
-                unsigned long long cur = os.key[h];
-                if (cur == 0) {
-                    cur = atomicCAS(&os.key[h], 0ull, k);
-                    if (cur == 0) {  // this lane made the slot: the next record is the pair's
-                        const uint32_t q = atomicAdd(&os.ctl[0], 1u);
-                        if (q < os.max_nodes) os.idx[h] = q;
-                        else bad = kOriginFull;
-                        cur = k;
+        const uint32_t r = resource[i];
+        const bool creates = r < nres && kind[i] != SGA_KIND_EXIT;
+#pragma unroll
+        for (int pk = 0; pk < kPairKinds; ++pk) {
+            if (!ids.id[pk]) continue;
+            const PairState &os = pt.t[pk];
+            const uint32_t o = ids.id[pk][i];
+            uint32_t slot = kPairNone;
+            if (o > os.n_ids) {
+                bad |= kPairBadId;
+            } else if (o && creates) {
+                const unsigned long long k = pair_key(r, o);
+                uint32_t h = pair_home(os, k);
+                for (uint32_t step = 0; step <= os.mask; ++step, h = (h + 1) & os.mask) {
+                    unsigned long long cur = os.key[h];
+                    if (cur == 0) {
+                        cur = atomicCAS(&os.key[h], 0ull, k);
+                        if (cur == 0) {  // this lane made the slot: the next record is the pair's
+                            const uint32_t q = atomicAdd(os.cnt, 1u);
+                            if (q < os.max_nodes) os.idx[h] = q;
+                            else bad |= kPairFull;
+                            cur = k;
+                        }
+                    }
+                    if (cur == k) {
+                        slot = h;
+                        break;
                     }
                 }
-                if (cur == k) {
-                    slot = h;
-                    break;
-                }
+                if (slot == kPairNone) bad |= kPairFull;
+                else if (os.born[slot] > seq_base + i)  // births only fall: a pair born earlier needs no atomic
+                    atomicMin(&os.born[slot], (unsigned long long)(seq_base + i));
             }
-            if (slot == kOriginNone) bad = kOriginFull;
-            else if (os.born[slot] > seq_base + i)  // births only fall: a pair born earlier needs no atomic
-                atomicMin(&os.born[slot], (unsigned long long)(seq_base + i));
+            ids.slot[pk][i] = slot;
         }
-        oslot[i] = slot;
     }
     bad = wave_or_u32(bad);
     if ((threadIdx.x & 63) == 0 && bad) {
-        atomicOr(&os.ctl[1], bad);
-        if (gate) atomicOr(gate, kGateBad | ((bad & kOriginFull) ? kGateFull : 0u) | ((bad & kOriginBadId) ? kGateOrigin : 0u));
+        atomicOr(&pt.ctl[0], bad);
+        if (gate) atomicOr(gate, kGateBad | ((bad & kPairFull) ? kGateFull : 0u) | ((bad & kPairBadId) ? kGateOrigin : 0u));
     }
 }
 
-// A refused chunk takes its claims back: pairs born in it are unborn again (their records stay reserved for
-// them), slots left without a record are dead, the record counter stops at the table's size.
-__global__ __launch_bounds__(kT) void k_orollback(OriginState os, uint64_t seq_base, const uint32_t *gate) {
+// A refused chunk takes its claims back, in every table it claimed from (kinds: bit k = the chunk carried ids of
+// kind k): pairs born in it are unborn again (their records stay reserved for them), slots left without a
+// record are dead, the record counter stops at the table's size.
+__global__ __launch_bounds__(kT) void k_orollback(PairTabs pt, uint32_t kinds, uint64_t seq_base, const uint32_t *gate) {
     if (gate && !(*gate & kGateBad)) return;
     const uint32_t h = blockIdx.x * kT + threadIdx.x;
-    if (h == 0 && os.ctl[0] > os.max_nodes) os.ctl[0] = os.max_nodes;
-    if (h > os.mask) return;
-    const unsigned long long k = os.key[h];
-    if (k == 0 || (k & kOriginDead)) return;
-    if (os.born[h] != kOriginUnborn && os.born[h] >= seq_base) os.born[h] = kOriginUnborn;
-    if (os.idx[h] == kOriginNone) os.key[h] = k | kOriginDead;
+#pragma unroll
+    for (int pk = 0; pk < kPairKinds; ++pk) {
+        if (!(kinds >> pk & 1u)) continue;
+        const PairState &os = pt.t[pk];
+        if (h == 0 && *os.cnt > os.max_nodes) *os.cnt = os.max_nodes;
+        if (h > os.mask) continue;
+        const unsigned long long k = os.key[h];
+        if (k == 0 || (k & kPairDead)) continue;
+        if (os.born[h] != kPairUnborn && os.born[h] >= seq_base) os.born[h] = kPairUnborn;
+        if (os.idx[h] == kPairNone) os.key[h] = k | kPairDead;
+    }
 }
 
 // small chunks: one lane, arrival order
-__global__ void k_oseq(OriginState os, int64_t max_rt, uint32_t nres, uint64_t seq_base, const uint32_t *oslot,
+__global__ void k_oseq(PairTabs pt, PairIds ids, int64_t max_rt, uint32_t nres, uint64_t seq_base,
                        const uint8_t *__restrict__ kind, const uint32_t *__restrict__ resource,
-                       const uint32_t *__restrict__ origin, const uint32_t *__restrict__ ts_off, int64_t ts_base,
+                       const uint32_t *__restrict__ ts_off, int64_t ts_base,
                        const int32_t *__restrict__ acquire, const uint8_t *__restrict__ flags,
                        const int64_t *__restrict__ rt_in, const int8_t *__restrict__ decision, uint32_t n,
                        const uint8_t *__restrict__ oruled) {
@@ -1543,18 +1594,21 @@ __global__ void k_oseq(OriginState os, int64_t max_rt, uint32_t nres, uint64_t s
     const Ctx c{FlowState{}, max_rt};
     for (uint32_t i = 0; i < n; ++i) {
         if (oruled && resource[i] < nres && oruled[resource[i]]) continue;  // counted by its replay
-        const uint32_t q = origin_node_of(os, i, kind[i], resource[i], origin[i], nres, seq_base, oslot);
-        if (q == kOriginNone) continue;
-        origin_event(c, os.node + (size_t)q * kNodeWords, origin_pack(i, kind, ts_off, acquire, flags, decision), ts_base,
-                     rt_in);
+        for (int pk = 0; pk < kPairKinds; ++pk) {
+            if (!ids.id[pk]) continue;
+            const uint32_t q = pair_node_of(pt.t[pk], i, kind[i], resource[i], ids.id[pk][i], nres, seq_base, ids.slot[pk]);
+            if (q == kPairNone) continue;
+            origin_event(c, pt.t[pk].node + (size_t)q * kNodeWords, origin_pack(i, kind, ts_off, acquire, flags, decision),
+                         ts_base, rt_in);
+        }
     }
 }
 
-// sort elements: (node record, arrival index); events without a node sort last under max_nodes
-__global__ __launch_bounds__(kT) void k_oelems(OriginState os, uint32_t nres, uint64_t seq_base, const uint32_t *oslot,
+// sort elements: (node record, arrival index), one per event and id array the chunk carries -- n elements of the
+// first array present, then n of the second; elements without a node sort last under pt.total
+__global__ __launch_bounds__(kT) void k_oelems(PairTabs pt, PairIds ids, uint32_t nres, uint64_t seq_base,
                                                const uint8_t *__restrict__ kind,
                                                const uint32_t *__restrict__ resource,
-                                               const uint32_t *__restrict__ origin,
                                                const uint32_t *__restrict__ ts_off,
                                                const int32_t *__restrict__ acquire,
                                                const uint8_t *__restrict__ flags,
@@ -1563,23 +1617,36 @@ __global__ __launch_bounds__(kT) void k_oelems(OriginState os, uint32_t nres, ui
                                                const uint8_t *__restrict__ oruled) {
     const uint32_t i = blockIdx.x * kT + threadIdx.x;
     if (i >= n) return;
-    uint32_t q = kOriginNone;
-    // (an origin-ruled resource's origin nodes are counted by its replay, in arrival order)
-    if (gate_is(gate, kGateBad, 0) && !(oruled && resource[i] < nres && oruled[resource[i]])) q = origin_node_of(os, i, kind[i], resource[i], origin[i], nres, seq_base, oslot);
-    keys[i] = q == kOriginNone ? os.max_nodes : q;
-    pay[i] = q == kOriginNone ? Payload{i, 0, 0, 0} : origin_pack(i, kind, ts_off, acquire, flags, decision);
+    // (a pair-ruled resource's pair nodes are counted by its replay, in arrival order)
+    const bool counted = gate_is(gate, kGateBad, 0) && !(oruled && resource[i] < nres && oruled[resource[i]]);
+    uint32_t e = i;
+#pragma unroll
+    for (int pk = 0; pk < kPairKinds; ++pk) {
+        if (!ids.id[pk]) continue;
+        uint32_t q = kPairNone;
+        if (counted) q = pair_node_of(pt.t[pk], i, kind[i], resource[i], ids.id[pk][i], nres, seq_base, ids.slot[pk]);
+        keys[e] = q == kPairNone ? pt.total : q + (pk ? pt.base1 : 0u);
+        pay[e] = q == kPairNone ? Payload{i, 0, 0, 0} : origin_pack(i, kind, ts_off, acquire, flags, decision);
+        e += n;
+    }
+}
+
+// the node record a sort key stands for
+__device__ __forceinline__ int64_t *pair_node_at(const PairTabs &pt, uint32_t k) {
+    return k < pt.base1 ? pt.t[kPairOrigin].node + (size_t)k * kNodeWords
+                        : pt.t[kPairContext].node + (size_t)(k - pt.base1) * kNodeWords;
 }
 
 // segment heads: a node with fewer than kOriginLong events is applied here by the head's lane, event by event;
 // longer segments are listed for k_olong
-__global__ __launch_bounds__(kT) void k_oshort(OriginState os, int64_t max_rt, const uint32_t *__restrict__ keys,
+__global__ __launch_bounds__(kT) void k_oshort(PairTabs pt, int64_t max_rt, const uint32_t *__restrict__ keys,
                                                const Payload *__restrict__ pay, uint32_t n, uint32_t *olong,
                                                int64_t ts_base, const int64_t *__restrict__ rt_in,
                                                const uint32_t *gate) {
     const uint32_t p = blockIdx.x * kT + threadIdx.x;
     if (p >= n || !gate_is(gate, kGateBad, 0)) return;
     const uint32_t k = keys[p];
-    if (k >= os.max_nodes || (p && keys[p - 1] == k)) return;
+    if (k >= pt.total || (p && keys[p - 1] == k)) return;
     uint32_t lo = p + 1, hi = n;  // the first position past the node's elements
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
@@ -1588,13 +1655,13 @@ __global__ __launch_bounds__(kT) void k_oshort(OriginState os, int64_t max_rt, c
     }
     const uint32_t len = lo - p;
     if (len >= kOriginLong) {
-        const uint32_t q = atomicAdd(&os.ctl[2], 1u);
+        const uint32_t q = atomicAdd(&pt.ctl[1], 1u);
         olong[2 * q] = p;
         olong[2 * q + 1] = len;
         return;
     }
     const Ctx c{FlowState{}, max_rt};
-    int64_t *node = os.node + (size_t)k * kNodeWords;
+    int64_t *node = pair_node_at(pt, k);
     for (uint32_t j = p; j < p + len; ++j) origin_event(c, node, pay[j], ts_base, rt_in);
 }
 
@@ -1602,7 +1669,7 @@ __global__ __launch_bounds__(kT) void k_oshort(OriginState os, int64_t max_rt, c
 // not decrease (nor go below the previous tile's last) and span fewer than kEnBuckets 500 ms buckets is reduced
 // per bucket in LDS and applied bucket by bucket -- the same window rotations as event by event, a 500 ms bucket
 // lying inside one 1 s minute bucket; any other tile is applied event by event by one lane.
-__global__ __launch_bounds__(kOriginT) void k_olong(OriginState os, int64_t max_rt, const uint32_t *__restrict__ keys,
+__global__ __launch_bounds__(kOriginT) void k_olong(PairTabs pt, int64_t max_rt, const uint32_t *__restrict__ keys,
                                                     const Payload *__restrict__ pay, const uint32_t *__restrict__ olong,
                                                     int64_t ts_base, const int64_t *__restrict__ rt_in,
                                                     const uint32_t *gate) {
@@ -1613,11 +1680,11 @@ __global__ __launch_bounds__(kOriginT) void k_olong(OriginState os, int64_t max_
     __shared__ int64_t prev_last;
     if (!gate_is(gate, kGateBad, 0)) return;
     const Ctx c{FlowState{}, max_rt};
-    const uint32_t nlong = os.ctl[2];
+    const uint32_t nlong = pt.ctl[1];
     typedef unsigned long long u64;
     for (uint32_t s = blockIdx.x; s < nlong; s += gridDim.x) {
         const uint32_t p = olong[2 * s], len = olong[2 * s + 1];
-        int64_t *node = os.node + (size_t)keys[p] * kNodeWords;
+        int64_t *node = pair_node_at(pt, keys[p]);
         if (threadIdx.x == 0) prev_last = INT64_MIN;
         for (uint32_t base = 0; base < len; base += kOriginTile) {
             const uint32_t cnt = min((uint32_t)kOriginTile, len - base);
@@ -1700,22 +1767,22 @@ __global__ __launch_bounds__(kOriginT) void k_olong(OriginState os, int64_t max_
     }
 }
 
-// the origins with a node on resource r (at most cap written, all counted)
-__global__ __launch_bounds__(kT) void k_onodes(OriginState os, uint32_t r, uint32_t *out, uint32_t cap, uint32_t *count) {
+// the ids (origins, contexts) with a node on resource r in one table (at most cap written, all counted)
+__global__ __launch_bounds__(kT) void k_onodes(PairState os, uint32_t r, uint32_t *out, uint32_t cap, uint32_t *count) {
     const uint32_t h = blockIdx.x * kT + threadIdx.x;
     if (h > os.mask) return;
     const unsigned long long k = os.key[h];
-    if ((k & kOriginDead) || (uint32_t)(k >> 32) != r + 1u || os.born[h] == kOriginUnborn) return;
+    if ((k & kPairDead) || (uint32_t)(k >> 32) != r + 1u || os.born[h] == kPairUnborn) return;
     const uint32_t q = atomicAdd(count, 1u);
     if (q < cap) out[q] = (uint32_t)k;
 }
 
-__global__ void k_set_octx(OriginCtx *dst, OriginCtx v) { *dst = v; }
+__global__ void k_set_octx(PairCtx *dst, PairCtx v) { *dst = v; }
 
-__global__ void k_ofind(OriginState os, uint32_t r, uint32_t o, uint32_t *out) {
+__global__ void k_ofind(PairState os, uint32_t r, uint32_t o, uint32_t *out) {
     if (threadIdx.x || blockIdx.x) return;
-    const uint32_t h = origin_find(os, origin_key(r, o));
-    *out = (h == kOriginNone || os.born[h] == kOriginUnborn) ? kOriginNone : os.idx[h];
+    const uint32_t h = pair_find(os, pair_key(r, o));
+    *out = (h == kPairNone || os.born[h] == kPairUnborn) ? kPairNone : os.idx[h];
 }
 
 // ------------------------------------------------------------------ classify
@@ -2184,13 +2251,14 @@ __device__ __forceinline__ void replay_event(const Ctx &c, const FlowScratch &sc
     }
 }
 
-// One event of an origin-ruled resource (group_event): the slot chain with the event's origin -- its rules select
-// their node by limitApp (chain_entry<., true>) -- and, in the same arrival order, StatisticSlot's adds on the
-// origin node (the statistics pass leaves such resources alone).  A call: the callers keep their registers.
+// One event of a pair-ruled resource (group_event): the slot chain with the event's origin and context -- its rules
+// select their node by limitApp and, for strategy CHAIN, by context (chain_entry<., true>) -- and, in the same
+// arrival order, StatisticSlot's adds on the origin node and on the context's DefaultNode (the statistics pass
+// leaves such resources alone).  A call: the callers keep their registers.
 __device__ __noinline__ void origin_group_event(const Ctx &c, const FlowScratch &sc, uint32_t res, const Payload &q,
                                                 int64_t ts_base, const int64_t *__restrict__ rt_in, int8_t *decision,
                                                 int32_t *wait_ms) {
-    const OriginCtx &oc = *c.st.octx;
+    const PairCtx &oc = *c.st.octx;
     const int64_t t = ts_base + (int64_t)q.ts_off;
     const uint32_t idx = q.idx & F_IDX;
     const int a = (int)(q.acq_prio & 0x7FFFFFFFu);
@@ -2206,9 +2274,7 @@ __device__ __noinline__ void origin_group_event(const Ctx &c, const FlowScratch 
     } else if (hp && (fl & SGA_EV_PARAM_LIST) && sc.pvals) {
         pa = PArgs{sc.pvals + (pv >> 32), (uint32_t)pv};
     }
-    const uint32_t o = oc.origin ? oc.origin[idx] : 0;
-    const uint32_t rec = origin_node_of(oc.os, idx, kd, res, o, c.st.nres, oc.seq_base, oc.oslot);
-    int64_t *onode = rec == kOriginNone ? nullptr : oc.os.node + (size_t)rec * kNodeWords;
+    const PairNodes pn = pair_nodes_of(oc, idx, kd, res, c.st.nres);
     uint32_t code = kd;
     if (kd == SGA_KIND_BLOCKED) {
         blocked_event(c, res, t, a);
@@ -2219,14 +2285,14 @@ __device__ __noinline__ void origin_group_event(const Ctx &c, const FlowScratch 
         if (fl & SGA_EV_ERROR) code |= 16u;
     } else {
         int64_t w = 0;
-        const OriginSel os{onode, o, oc.rule_lim + c.st.res[res].rule_off};
+        const OriginSel os{&pn, oc.rule_lim + c.st.res[res].rule_off, oc.rule_ctx + c.st.res[res].rule_off};
         const int8_t d = chain_entry<true, true>(c, res, res_global(c, res, c.st.res[res]), t, a,
                                                  (fl & SGA_EV_PRIORITIZED) != 0, hp, pv, &w, pa, idx, &os);
         decision[idx] = d;
         wait_ms[idx] = (int32_t)w;
         code |= (d == D_PASS ? 0u : d == D_PASS_WAIT ? 1u : 2u) << 2;
     }
-    if (onode) origin_event(c, onode, Payload{idx, q.ts_off, (uint32_t)a, code}, ts_base, rt_in);
+    pair_count(c, pn, Payload{idx, q.ts_off, (uint32_t)a, code}, ts_base, rt_in);
 }
 
 // One event of a RELATE group's replay (k_lflows inline, k_lgroup, k_lsmall): ClusterBuilderSlot.entry creates
@@ -6216,7 +6282,7 @@ FlowState FlowEngine::state() const {
     s.nprid = lru ? (uint32_t)d_psize.n : 0;
     s.ntslot = lru ? ntbase * (uint32_t)kMaxParamIdx : 0;
     s.seq_base = seq;
-    s.octx = has_origin_rules ? d_octx.p : nullptr;
+    s.octx = has_pair_rules ? d_octx.p : nullptr;
     return s;
 }
 
@@ -6465,20 +6531,27 @@ void FlowEngine::upload_res() {
 
 // FlowRuleManager.loadRules -> FlowRuleUtil.buildFlowRuleMap/generateRater: raters regenerated
 // (controller state reset), node statistics kept.  FlowRuleUtil.java:84-195
-int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint32_t *limit_app) {
+int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint32_t *limit_app, bool chain) {
     if (!nres) return SGA_EINVAL;
     for (size_t i = 0; limit_app && i < n; ++i)
-        if (limit_app[i] > n_origins && limit_app[i] < SGA_LIMIT_OTHER) return SGA_EINVAL;
+        if (limit_app[i] > ptab[kPairOrigin].n_ids && limit_app[i] < SGA_LIMIT_OTHER) return SGA_EINVAL;
+    const bool ordered = limit_app || chain;  // the loaders that know limitApp order like FlowRuleComparator
+    const uint32_t n_contexts = ptab[kPairContext].n_ids;
     std::vector<std::vector<FlowRuleDev>> per(nres);
-    std::vector<std::vector<uint8_t>> first(limit_app ? nres : 0);  // per rule: a non-default limitApp (sorts first)
-    std::vector<std::vector<uint32_t>> plim(limit_app ? nres : 0);  // per rule: the limitApp the replay selects by
+    std::vector<std::vector<uint8_t>> first(ordered ? nres : 0);  // per rule: a non-default limitApp (sorts first)
+    std::vector<std::vector<uint32_t>> plim(ordered ? nres : 0);  // per rule: the limitApp the replay selects by
+    std::vector<std::vector<uint32_t>> pctx(ordered ? nres : 0);  // per rule: a CHAIN rule's context, else 0
     int valid = 0;
     for (size_t i = 0; i < n; ++i) {
         const sga_flow_rule &r = rules[i];
         if (r.resource >= nres) continue;
         // FlowRuleUtil.isValidRule + checkStrategyField (:246-251): DIRECT, or RELATE (the binding layer turns a
-        // blank refResource into strategy -1); CHAIN and origin-specific limitApp are not served
-        bool ok = r.count >= 0 && r.grade >= 0 && r.control_behavior >= 0 && (r.strategy == 0 || r.strategy == 1);
+        // blank refResource into strategy -1); CHAIN only through sga_load_flow_rules_ctx, its refResource a
+        // registered context or a name no event can carry
+        bool ok = r.count >= 0 && r.grade >= 0 && r.control_behavior >= 0 &&
+                  (r.strategy == 0 || r.strategy == 1 ||
+                   (chain && r.strategy == 2 &&
+                    ((r.ref_resource >= 1 && r.ref_resource <= n_contexts) || r.ref_resource == SGA_CONTEXT_UNKNOWN)));
         if (ok && r.cluster_mode) {  // FlowRuleUtil.checkClusterField / checkClusterConcurrentField (:197-240)
             ok = r.cluster_flow_id > 0 && r.cluster_sample_count > 0 && r.cluster_window_ms > 0 &&
                  r.cluster_window_ms % r.cluster_sample_count == 0 && (r.grade != 1 || r.cluster_strategy == 0);
@@ -6514,6 +6587,10 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
         // A cluster-mode rule still asks the token service first (passCheck, :77-81): only its local fallback
         // looks for a node.
         if (lim == SGA_LIMIT_UNKNOWN) d.rel = nres + 1u;
+        // selectReferenceNode (FlowRuleChecker.java:96-116): so does a CHAIN rule whose refResource is the name of
+        // no registered context
+        const bool chain_unknown = r.strategy == 2 && r.ref_resource == SGA_CONTEXT_UNKNOWN;
+        if (chain_unknown) d.rel = nres + 1u;
         if (d.behavior == 1 || d.behavior == 3) {  // WarmUpController.construct, :83-106
             d.warning_token = j_d2i((double)r.warm_up_period_sec * r.count) / (cfg.cold_factor - 1);
             d.max_token = d.warning_token + j_d2i(2 * r.warm_up_period_sec * r.count / (1.0 + cfg.cold_factor));
@@ -6521,26 +6598,29 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
         }
         per[r.resource].push_back(d);
         // (an unknown limitApp is stored as "default" on a rule that never applies: its resource needs no replay)
-        if (limit_app) plim[r.resource].push_back(lim == SGA_LIMIT_UNKNOWN ? SGA_LIMIT_DEFAULT : lim);
-        if (limit_app) first[r.resource].push_back(lim != SGA_LIMIT_DEFAULT);
+        if (ordered) plim[r.resource].push_back(lim == SGA_LIMIT_UNKNOWN || chain_unknown ? SGA_LIMIT_DEFAULT : lim);
+        if (ordered) first[r.resource].push_back(lim != SGA_LIMIT_DEFAULT);
+        if (ordered) pctx[r.resource].push_back(r.strategy == 2 && !chain_unknown ? r.ref_resource : 0u);
         valid++;
     }
     // FlowRuleComparator (FlowRuleComparator.java:30-55) as a stable sort, for the loader that knows each rule's
     // limitApp: by (cluster mode, limitApp == default) -- cluster-mode rules last, and inside either half the
     // rules of a non-default limitApp first.  (The plain loader keeps the list order, as before.)
-    for (uint32_t r = 0; limit_app && r < nres; ++r) {
+    for (uint32_t r = 0; ordered && r < nres; ++r) {
         std::vector<size_t> ord(per[r].size());
         for (size_t k = 0; k < ord.size(); ++k) ord[k] = k;
         auto rank = [&](size_t k) { return (per[r][k].cluster ? 2 : 0) + (first[r][k] ? 0 : 1); };
         std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rank(a) < rank(b); });
         std::vector<FlowRuleDev> sorted;
-        std::vector<uint32_t> slim;
+        std::vector<uint32_t> slim, sctx;
         for (size_t k : ord) {
             sorted.push_back(per[r][k]);
             slim.push_back(plim[r][k]);
+            sctx.push_back(pctx[r][k]);
         }
         per[r].swap(sorted);
         plim[r].swap(slim);
+        pctx[r].swap(sctx);
     }
     // RELATE groups: the components of the (resource, refResource) pairs -- a resource whose only RELATE rule
     // names itself is a component of one -- each led by its smallest member.  A group's events are decided in
@@ -6561,18 +6641,26 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
                 grouped[r] = grouped[d.rel - 1u] = 1;
             }
         // a resource with a rule limited to an origin or to "other" is coupled through the ClusterNode its
-        // "default" rules read and the origin nodes the others read: a group of its own (or its RELATE group's)
+        // "default" rules read and the origin nodes the others read, and so is one with a CHAIN rule, through its
+        // ClusterNode and the DefaultNodes those rules read: a group of its own (or its RELATE group's)
         std::vector<uint8_t> oruled(nres, 0);
-        has_origin_rules = false;
-        for (uint32_t r = 0; limit_app && r < nres; ++r)
+        has_pair_rules = false;
+        for (uint32_t r = 0; ordered && r < nres; ++r) {
             for (uint32_t l : plim[r])
                 if (l != SGA_LIMIT_DEFAULT) oruled[r] = grouped[r] = 1;
-        for (uint32_t r = 0; r < nres; ++r) has_origin_rules |= oruled[r] != 0;
+            for (uint32_t cx : pctx[r])
+                if (cx) oruled[r] = grouped[r] = 1;
+        }
+        for (uint32_t r = 0; r < nres; ++r) has_pair_rules |= oruled[r] != 0;
         h_rule_lim.clear();
-        if (has_origin_rules) {
+        h_rule_ctx.clear();
+        if (has_pair_rules) {
             for (uint32_t r = 0; r < nres; ++r) h_rule_lim.insert(h_rule_lim.end(), plim[r].begin(), plim[r].end());
+            for (uint32_t r = 0; r < nres; ++r) h_rule_ctx.insert(h_rule_ctx.end(), pctx[r].begin(), pctx[r].end());
             SGA_HIP_CHECK(hipStreamSynchronize(stream));
             d_rule_lim.alloc(std::max<size_t>(h_rule_lim.size(), 1));
+            d_rule_ctx.alloc(std::max<size_t>(h_rule_ctx.size(), 1));
+            SGA_HIP_CHECK(hipMemcpy(d_rule_ctx.p, h_rule_ctx.data(), h_rule_ctx.size() * 4, hipMemcpyHostToDevice));
             d_oruled.alloc(nres);
             if (!d_octx.p) d_octx.alloc(1);
             SGA_HIP_CHECK(hipMemcpy(d_rule_lim.p, h_rule_lim.data(), h_rule_lim.size() * 4, hipMemcpyHostToDevice));
@@ -7186,7 +7274,7 @@ int FlowEngine::ensure_scratch() {
 int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire,
                              const uint8_t *flags, const int64_t *rt, const uint64_t *param, const uint32_t *ts_off,
                              int64_t lo, uint32_t m, int8_t *decision, int32_t *wait_ms, const uint64_t *pvals,
-                             size_t npvals, const uint32_t *origin) {
+                             size_t npvals, const uint32_t *origin, const uint32_t *context) {
     auto a8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
     const size_t o_kind = 0, o_flags = a8(o_kind + kSmallEvents), o_res = a8(o_flags + kSmallEvents),
                  o_ts = o_res + 4 * kSmallEvents, o_acq = o_ts + 4 * kSmallEvents, o_rt = o_acq + 4 * kSmallEvents,
@@ -7225,11 +7313,17 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
     const int32_t *dacq = (const int32_t *)(d + o_acq);
     const int64_t *drt = (const int64_t *)(d + o_rt);
     const uint64_t *dpar = (const uint64_t *)(d + o_param), *dvals = npvals ? (const uint64_t *)(d + o_vals) : nullptr;
-    if (origin) {  // origin nodes exist ahead of every check; a full table refuses the chunk
-        SGA_HIP_CHECK(hipMemcpyAsync(d_origin.p, origin, 4 * (size_t)m, hipMemcpyHostToDevice, stream));
-        if (const int rc = origin_claim(dk, dres, d_origin.p, m, nullptr, stream)) return rc;
-    }
-    origin_ctx(origin ? d_origin.p : nullptr, stream);
+    const uint32_t *hids[kPairKinds] = {origin, context}, *ids[kPairKinds] = {nullptr, nullptr};
+    for (int k = 0; k < kPairKinds; ++k)
+        if (hids[k]) {
+            SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k], 4 * (size_t)m, hipMemcpyHostToDevice, stream));
+            ids[k] = ptab[k].ids.p;
+        }
+    const bool pairs = origin || context;
+    // pair nodes exist ahead of every check; a full table refuses the chunk
+    if (pairs)
+        if (const int rc = pair_claim(dk, dres, ids, m, nullptr, stream)) return rc;
+    pair_ctx(ids, stream);
     lru_prepare(dk, dres, dfl, dpar, dvals, m, stream);  // CacheMap capacity
     FlowScratch fs = sc;
     fs.in_kind = dk;
@@ -7241,8 +7335,8 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
                        dts, lo, dacq, drt, m, (int8_t *)(d + o_dec), (int32_t *)(d + o_wait), (uint32_t *)(d + o_ovf),
                        maps ? 0 : 1);
     SGA_HIP_CHECK(hipGetLastError());
-    if (origin)
-        origin_apply(dk, dres, d_origin.p, dts, lo, dacq, dfl, drt, (const int8_t *)(d + o_dec), m, nullptr, true, stream);
+    if (pairs)
+        pair_apply(dk, dres, ids, dts, lo, dacq, dfl, drt, (const int8_t *)(d + o_dec), m, nullptr, true, stream);
     if (copy) SGA_HIP_CHECK(hipMemcpyAsync(h + o_dec, d + o_dec, all_bytes - o_dec, hipMemcpyDeviceToHost, stream));
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
     std::memcpy(decision, h + o_dec, m);
@@ -7281,14 +7375,19 @@ FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *
 
 int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int64_t *ts, const int32_t *acquire,
                        const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
-                       int32_t *wait_ms, const uint64_t *pvals, size_t npvals, const uint32_t *origin) {
+                       int32_t *wait_ms, const uint64_t *pvals, size_t npvals, const uint32_t *origin,
+                       const uint32_t *context) {
     if (!nres) return SGA_EINVAL;
     if (n == 0) return 0;
-    if (origin) {  // an id past the registered origins refuses the call
-        if (!n_origins) return SGA_EINVAL;
+    const uint32_t *hids[kPairKinds] = {origin, context}, *ids[kPairKinds] = {nullptr, nullptr};
+    for (int k = 0; k < kPairKinds; ++k) {
+        if (!hids[k]) continue;  // an id past the registered ones refuses the call
+        if (!ptab[k].n_ids) return SGA_EINVAL;
         for (size_t i = 0; i < n; ++i)
-            if (origin[i] > n_origins) return SGA_EINVAL;
+            if (hids[k][i] > ptab[k].n_ids) return SGA_EINVAL;
+        ids[k] = ptab[k].ids.p;
     }
+    const bool pairs = origin || context;
     // Collection / array arguments (SGA_EV_PARAM_LIST): the value array goes to the device once;
     // chunks holding such events are replayed in arrival order by one lane (k_lseq)
     // and whole argument vectors (SGA_EV_ARGS: word pairs, lists inside param_values)
@@ -7349,8 +7448,8 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                                             rt ? rt + b : nullptr, param ? param + b : nullptr, off.data(), lo,
                                             (uint32_t)m, decision + b, wait_ms ? wait_ms + b : nullptr,
                                             has_list ? pvals : nullptr, has_list ? npvals : 0,
-                                            origin ? origin + b : nullptr)) {
-                seq += m;  // a chunk that failed part-way keeps its sequence numbers (origin births)
+                                            origin ? origin + b : nullptr, context ? context + b : nullptr)) {
+                seq += m;  // a chunk that failed part-way keeps its sequence numbers (pair births)
                 return rc;
             }
             b += m;
@@ -7367,17 +7466,19 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         else SGA_HIP_CHECK(hipMemsetAsync(d_rt.p, 0, m * 8, stream));
         if (param) SGA_HIP_CHECK(hipMemcpyAsync(d_param.p, param + b, m * 8, hipMemcpyHostToDevice, stream));
         else SGA_HIP_CHECK(hipMemsetAsync(d_param.p, 0, m * 8, stream));
-        if (origin) {  // origin nodes exist ahead of every check; a full table refuses the chunk
-            SGA_HIP_CHECK(hipMemcpyAsync(d_origin.p, origin + b, m * 4, hipMemcpyHostToDevice, stream));
-            if (const int rc = origin_claim(d_kind.p, d_resid.p, d_origin.p, (uint32_t)m, nullptr, stream)) return rc;
-        }
+        for (int k = 0; k < kPairKinds; ++k)
+            if (hids[k])
+                SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k] + b, m * 4, hipMemcpyHostToDevice, stream));
+        // pair nodes exist ahead of every check; a full table refuses the chunk
+        if (pairs)
+            if (const int rc = pair_claim(d_kind.p, d_resid.p, ids, (uint32_t)m, nullptr, stream)) return rc;
         SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, stream));
         // per chunk: a probe sequence that overflowed in an earlier (failed) batch must not fail
         // every later one.  A failed batch has been partly applied (its node and breaker updates
         // stay); the call reports -ENOMEM.
         SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, stream));
         // CacheMap capacity: owners that could pass theirs switch to LRU mode (both paths below)
-        origin_ctx(origin ? d_origin.p : nullptr, stream);
+        pair_ctx(ids, stream);
         lru_prepare(d_kind.p, d_resid.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
                     any_list ? d_pvals.p : nullptr, (uint32_t)m, stream);
         const FlowState st = state();
@@ -7389,9 +7490,9 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                                d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_param.p, (uint32_t)m, d_dec.p,
                                d_wait.p, has_list ? d_pvals.p : nullptr);
             SGA_HIP_CHECK(hipGetLastError());
-            if (origin)
-                origin_apply(d_kind.p, d_resid.p, d_origin.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
-                             nullptr, false, stream);
+            if (pairs)
+                pair_apply(d_kind.p, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
+                           nullptr, false, stream);
             SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
             if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
             uint32_t ovf = 0;
@@ -7454,9 +7555,9 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
             hipLaunchKernelGGL(k_entry_stats, dim3(1), dim3(kEnTile), 0, stream, st, (int64_t)cfg.statistic_max_rt,
                                d_kind.p, d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m);
         SGA_HIP_CHECK(hipGetLastError());
-        if (origin)  // origin-node statistics from the finished decisions
-            origin_apply(d_kind.p, d_resid.p, d_origin.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
-                         nullptr, false, stream);
+        if (pairs)  // pair-node statistics from the finished decisions
+            pair_apply(d_kind.p, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
+                       nullptr, false, stream);
         SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
         if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
         uint32_t ovf = 0;
@@ -7515,8 +7616,11 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
                               const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags_in,
                               const int64_t *d_rt_in, const uint64_t *d_param_in, size_t n,
                               const uint64_t *d_param_values, size_t n_values, int8_t *d_decision, int32_t *d_wait,
-                              hipStream_t s, const uint32_t *d_origin_in) {
-    if (!nres || (d_origin_in && !n_origins)) return SGA_EINVAL;
+                              hipStream_t s, const uint32_t *d_origin_in, const uint32_t *d_context_in) {
+    if (!nres || (d_origin_in && !ptab[kPairOrigin].n_ids) || (d_context_in && !ptab[kPairContext].n_ids))
+        return SGA_EINVAL;
+    const uint32_t *ids[kPairKinds] = {d_origin_in, d_context_in};
+    const bool pairs = d_origin_in || d_context_in;
     if (n == 0) return 0;
     if (n > cfg.max_batch) return SGA_ERANGE;
     if (const int rc = ensure_scratch()) return rc;
@@ -7543,9 +7647,9 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     const uint32_t gb = std::min<uint32_t>(nb, 1024);
     hipLaunchKernelGGL(k_lgate, dim3(gb), dim3(kT), 0, s, d_kind_in, d_resource, d_acquire, flags_p, param_p, m, nres,
                        (int)sys.check, (uint64_t)(d_param_values ? n_values : 0), d_gate.p, d_param_values);
-    if (d_origin_in)  // origin nodes exist ahead of every check; a full table or a bad id closes the gate
-        if (const int rc = origin_claim(d_kind_in, d_resource, d_origin_in, m, d_gate.p, s)) return rc;
-    origin_ctx(d_origin_in, s);
+    if (pairs)  // pair nodes exist ahead of every check; a full table or a bad id closes the gate
+        if (const int rc = pair_claim(d_kind_in, d_resource, ids, m, d_gate.p, s)) return rc;
+    pair_ctx(ids, s);
     lru_prepare(d_kind_in, d_resource, flags_p, param_p, d_param_values, m, s);  // CacheMap capacity
     FlowState st = state();
     st.gate = d_gate.p;
@@ -7596,9 +7700,9 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, s, st, (int64_t)cfg.statistic_max_rt, sys, d_kind_in,
                        d_resource, d_ts_off, ts_base, d_acquire, flags_p, rt_p, param_p, m, d_decision, wait_p,
                        d_param_values);
-    if (d_origin_in)  // origin-node statistics from the finished decisions (either path's)
-        origin_apply(d_kind_in, d_resource, d_origin_in, d_ts_off, ts_base, d_acquire, flags_p, rt_p, d_decision, m,
-                     d_gate.p, false, s);
+    if (pairs)  // pair-node statistics from the finished decisions (either path's)
+        pair_apply(d_kind_in, d_resource, ids, d_ts_off, ts_base, d_acquire, flags_p, rt_p, d_decision, m, d_gate.p,
+                   false, s);
     hipLaunchKernelGGL(k_lfail, dim3(gb), dim3(kT), 0, s, d_gate.p, d_overflow.p, d_gate.p + 1, m, d_decision, wait_p);
     SGA_HIP_CHECK(hipGetLastError());
     seq += n;
@@ -7654,126 +7758,173 @@ int FlowEngine::query_at(int64_t *nodes, uint32_t r, int64_t now, sga_node_view 
     return 0;
 }
 
-// ---- caller origins
-int FlowEngine::set_origins(uint32_t n, uint32_t max_nodes) {
+// ---- pair nodes: caller origins (kPairOrigin) and contexts (kPairContext)
+int FlowEngine::set_pairs(int kind, uint32_t n, uint32_t max_nodes) {
     if (!nres || n == 0 || n >= SGA_LIMIT_OTHER) return SGA_EINVAL;
-    // the default table: 16,384 records (66 MB) -- a choice, not a measurement
+    // the default table: 16,384 records (66 MB) -- a choice, not a measurement, for either kind
     if (max_nodes == 0) max_nodes = 1u << 14;
     if (max_nodes > (1u << 26)) return SGA_EINVAL;
-    if (n_origins) return (n == n_origins && max_nodes == max_onodes) ? 0 : SGA_EINVAL;  // fixed once set
+    PairTable &t = ptab[kind];
+    if (t.n_ids) return (n == t.n_ids && max_nodes == t.max_nodes) ? 0 : SGA_EINVAL;  // fixed once set
     uint32_t slots = 64;
     while (slots < 2 * (size_t)max_nodes) slots <<= 1;  // load <= 0.5
     const size_t cap = cfg.max_batch;
-    d_onode.alloc((size_t)max_nodes * kNodeWords);
-    d_okey.alloc(slots);
-    d_oborn.alloc(slots);
-    d_oidx.alloc(slots);
-    d_octl.alloc(4);
-    d_origin.alloc(cap);
-    d_oslot.alloc(cap);
-    d_olong.alloc(2 * (cap / kOriginLong + 1));
-    hipLaunchKernelGGL(k_init_nodes, dim3((max_nodes + kT - 1) / kT), dim3(kT), 0, stream, d_onode.p, max_nodes,
+    t.node.alloc((size_t)max_nodes * kNodeWords);
+    t.key.alloc(slots);
+    t.born.alloc(slots);
+    t.idx.alloc(slots);
+    t.ids.alloc(cap);
+    t.slot.alloc(cap);
+    const bool both = ptab[kind ^ 1].n_ids != 0;
+    if (!d_pctl.p) {
+        d_pctl.alloc(8);
+        SGA_HIP_CHECK(hipMemsetAsync(d_pctl.p, 0, d_pctl.bytes(), stream));
+    }
+    if (both) {
+        // a chunk with both arrays sorts two elements per event: the pipeline's buffers hold one
+        SGA_HIP_CHECK(hipStreamSynchronize(stream));
+        size_t hist = 0;
+        for (int b = 1; b <= 32; ++b) hist = std::max(hist, radix_hist_entries(2 * cap, b));
+        for (int k = 0; k < 2; ++k) {
+            d_pkeys[k].alloc(2 * cap);
+            d_ppay[k].alloc(2 * cap);
+            d_phist[k].alloc(hist);
+        }
+        d_ppart.alloc(scan_partials_needed(hist) + 16);
+    }
+    if (both || !d_olong.p) {
+        SGA_HIP_CHECK(hipStreamSynchronize(stream));
+        d_olong.alloc(2 * ((both ? 2 : 1) * cap / kOriginLong + 1));
+    }
+    hipLaunchKernelGGL(k_init_nodes, dim3((max_nodes + kT - 1) / kT), dim3(kT), 0, stream, t.node.p, max_nodes,
                        (int64_t)cfg.statistic_max_rt);
     SGA_HIP_CHECK(hipGetLastError());
-    SGA_HIP_CHECK(hipMemsetAsync(d_okey.p, 0, d_okey.bytes(), stream));
-    SGA_HIP_CHECK(hipMemsetAsync(d_oborn.p, 0xFF, d_oborn.bytes(), stream));
-    SGA_HIP_CHECK(hipMemsetAsync(d_oidx.p, 0xFF, d_oidx.bytes(), stream));
-    SGA_HIP_CHECK(hipMemsetAsync(d_octl.p, 0, d_octl.bytes(), stream));
+    SGA_HIP_CHECK(hipMemsetAsync(t.key.p, 0, t.key.bytes(), stream));
+    SGA_HIP_CHECK(hipMemsetAsync(t.born.p, 0xFF, t.born.bytes(), stream));
+    SGA_HIP_CHECK(hipMemsetAsync(t.idx.p, 0xFF, t.idx.bytes(), stream));
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
-    n_origins = n;
-    max_onodes = max_nodes;
-    oslots = slots;
+    t.n_ids = n;
+    t.max_nodes = max_nodes;
+    t.slots = slots;
     return 0;
 }
 
-OriginState FlowEngine::ostate() const {
-    return OriginState{d_onode.p, d_okey.p, d_oborn.p, d_oidx.p, d_octl.p, oslots - 1, max_onodes, n_origins};
+PairTabs FlowEngine::pstate() const {
+    PairTabs pt{};
+    for (int k = 0; k < kPairKinds; ++k) {
+        const PairTable &t = ptab[k];
+        if (!t.n_ids) continue;
+        pt.t[k] = PairState{t.node.p, t.key.p, t.born.p, t.idx.p, d_pctl.p + 2 + k, t.slots - 1, t.max_nodes, t.n_ids};
+    }
+    pt.ctl = d_pctl.p;
+    pt.base1 = ptab[kPairOrigin].max_nodes;
+    pt.total = pt.base1 + ptab[kPairContext].max_nodes;
+    return pt;
 }
 
-// The chunk's OriginCtx, when the loaded rules hold origin-ruled resources (origin null: every event has origin 0,
-// so only their "default" rules apply)
-void FlowEngine::origin_ctx(const uint32_t *origin, hipStream_t s) {
-    if (!has_origin_rules) return;
-    const OriginCtx h{ostate(), origin, d_oslot.p, d_rule_lim.p, d_oruled.p, (uint64_t)seq};
+// The chunk's PairCtx, when the loaded rules hold pair-ruled resources (ids[k] null: every event has id 0 of that
+// kind, so only rules that need none apply)
+void FlowEngine::pair_ctx(const uint32_t *const ids[kPairKinds], hipStream_t s) {
+    if (!has_pair_rules) return;
+    const PairCtx h{pstate(),
+                    {ids[0], ids[1]},
+                    {ptab[0].slot.p, ptab[1].slot.p},
+                    d_rule_lim.p,
+                    d_rule_ctx.p,
+                    d_oruled.p,
+                    (uint64_t)seq};
     hipLaunchKernelGGL(k_set_octx, dim3(1), dim3(1), 0, s, d_octx.p, h);
     SGA_HIP_CHECK(hipGetLastError());
 }
 
-int FlowEngine::origin_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin, uint32_t m,
-                             uint32_t *gate, hipStream_t s) {
-    const OriginState os = ostate();
-    SGA_HIP_CHECK(hipMemsetAsync(d_octl.p + 1, 0, 8, s));  // the chunk's error bits and long segments
-    hipLaunchKernelGGL(k_oclaim, dim3((m + kT - 1) / kT), dim3(kT), 0, s, os, kind, resource, origin, m, nres,
-                       (uint64_t)seq, d_oslot.p, gate);
+int FlowEngine::pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
+                           uint32_t m, uint32_t *gate, hipStream_t s) {
+    const PairTabs pt = pstate();
+    const PairIds pi{{ids[0], ids[1]}, {ptab[0].slot.p, ptab[1].slot.p}};
+    const uint32_t kinds = (ids[0] ? 1u : 0u) | (ids[1] ? 2u : 0u);
+    uint32_t rslots = 0;
+    for (int k = 0; k < kPairKinds; ++k)
+        if (ids[k]) rslots = std::max(rslots, ptab[k].slots);
+    SGA_HIP_CHECK(hipMemsetAsync(d_pctl.p, 0, 8, s));  // the chunk's error bits and long segments
+    hipLaunchKernelGGL(k_oclaim, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, kind, resource, m, nres,
+                       (uint64_t)seq, gate);
     if (gate) {  // device entry: the gate refuses the chunk, k_lfail reports it
-        hipLaunchKernelGGL(k_orollback, dim3((oslots + kT - 1) / kT), dim3(kT), 0, s, os, (uint64_t)seq, gate);
+        hipLaunchKernelGGL(k_orollback, dim3((rslots + kT - 1) / kT), dim3(kT), 0, s, pt, kinds, (uint64_t)seq, gate);
         SGA_HIP_CHECK(hipGetLastError());
         return 0;
     }
     uint32_t err = 0;
-    SGA_HIP_CHECK(hipMemcpyAsync(&err, d_octl.p + 1, 4, hipMemcpyDeviceToHost, s));
+    SGA_HIP_CHECK(hipMemcpyAsync(&err, d_pctl.p, 4, hipMemcpyDeviceToHost, s));
     SGA_HIP_CHECK(hipStreamSynchronize(s));
     if (!err) return 0;
-    hipLaunchKernelGGL(k_orollback, dim3((oslots + kT - 1) / kT), dim3(kT), 0, s, os, (uint64_t)seq, nullptr);
+    hipLaunchKernelGGL(k_orollback, dim3((rslots + kT - 1) / kT), dim3(kT), 0, s, pt, kinds, (uint64_t)seq, nullptr);
     SGA_HIP_CHECK(hipGetLastError());
     SGA_HIP_CHECK(hipStreamSynchronize(s));
-    return (err & kOriginBadId) ? SGA_EINVAL : SGA_ENOMEM;
+    return (err & kPairBadId) ? SGA_EINVAL : SGA_ENOMEM;
 }
 
-void FlowEngine::origin_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin,
-                              const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
-                              const int64_t *rt, const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq_lane,
-                              hipStream_t s) {
-    const OriginState os = ostate();
+void FlowEngine::pair_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
+                            const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
+                            const int64_t *rt, const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq_lane,
+                            hipStream_t s) {
+    const PairTabs pt = pstate();
+    const PairIds pi{{ids[0], ids[1]}, {ptab[0].slot.p, ptab[1].slot.p}};
     const int64_t max_rt = (int64_t)cfg.statistic_max_rt;
     if (seq_lane) {
-        hipLaunchKernelGGL(k_oseq, dim3(1), dim3(64), 0, s, os, max_rt, nres, (uint64_t)seq, d_oslot.p, kind, resource,
-                           origin, ts_off, ts_base, acquire, flags, rt, decision, m,
-                           has_origin_rules ? d_oruled.p : nullptr);
+        hipLaunchKernelGGL(k_oseq, dim3(1), dim3(64), 0, s, pt, pi, max_rt, nres, (uint64_t)seq, kind, resource, ts_off,
+                           ts_base, acquire, flags, rt, decision, m, has_pair_rules ? d_oruled.p : nullptr);
         SGA_HIP_CHECK(hipGetLastError());
         return;
     }
-    // the chunk's decisions are final: the pipeline's sort buffers are free again
-    const uint32_t nb = (m + kT - 1) / kT;
-    hipLaunchKernelGGL(k_oelems, dim3(nb), dim3(kT), 0, s, os, nres, (uint64_t)seq, d_oslot.p, kind, resource, origin,
-                       ts_off, acquire, flags, decision, m, sc.keys[0], sc.pay[0], gate,
-                       has_origin_rules ? d_oruled.p : nullptr);
+    // the chunk's decisions are final: the pipeline's sort buffers are free again.  They hold one element per
+    // event; a chunk with both arrays has two, and sorts in the pass's own buffers
+    const bool two = ids[0] && ids[1];
+    const uint32_t ne = two ? 2 * m : m;
+    uint32_t *k0 = two ? d_pkeys[0].p : sc.keys[0], *k1 = two ? d_pkeys[1].p : sc.keys[1];
+    Payload *p0 = two ? d_ppay[0].p : sc.pay[0], *p1 = two ? d_ppay[1].p : sc.pay[1];
+    RadixScratch rs2{nullptr, nullptr, d_phist[0].p, d_phist[1].p, d_ppart.p};
+    hipLaunchKernelGGL(k_oelems, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, nres, (uint64_t)seq, kind, resource,
+                       ts_off, acquire, flags, decision, m, k0, p0, gate, has_pair_rules ? d_oruled.p : nullptr);
     int bits = 1;
-    while (((uint64_t)1 << bits) < (uint64_t)max_onodes + 1) ++bits;
-    const int np = radix_sort_pairs(sc.keys[0], sc.pay[0], sc.keys[1], sc.pay[1], m, bits, sc.radix, s);
-    const uint32_t *keys = sc.keys[np & 1];
-    const Payload *pay = sc.pay[np & 1];
-    hipLaunchKernelGGL(k_oshort, dim3(nb), dim3(kT), 0, s, os, max_rt, keys, pay, m, d_olong.p, ts_base, rt, gate);
-    hipLaunchKernelGGL(k_olong, dim3(std::max<uint32_t>(1, std::min<uint32_t>(2048, m / kOriginLong))), dim3(kOriginT),
-                       0, s, os, max_rt, keys, pay, d_olong.p, ts_base, rt, gate);
+    while (((uint64_t)1 << bits) < (uint64_t)pt.total + 1) ++bits;
+    const int np = radix_sort_pairs(k0, p0, k1, p1, ne, bits, two ? rs2 : sc.radix, s);
+    const uint32_t *keys = (np & 1) ? k1 : k0;
+    const Payload *pay = (np & 1) ? p1 : p0;
+    hipLaunchKernelGGL(k_oshort, dim3((ne + kT - 1) / kT), dim3(kT), 0, s, pt, max_rt, keys, pay, ne, d_olong.p, ts_base,
+                       rt, gate);
+    hipLaunchKernelGGL(k_olong, dim3(std::max<uint32_t>(1, std::min<uint32_t>(2048, ne / kOriginLong))), dim3(kOriginT),
+                       0, s, pt, max_rt, keys, pay, d_olong.p, ts_base, rt, gate);
     SGA_HIP_CHECK(hipGetLastError());
 }
 
-int FlowEngine::query_origin(uint32_t r, uint32_t o, int64_t now, sga_node_view *out) {
-    if (!n_origins || r >= nres || o == 0 || o > n_origins || now < 0 || !out) return SGA_EINVAL;
+int FlowEngine::query_pair(int kind, uint32_t r, uint32_t o, int64_t now, sga_node_view *out) {
+    const PairTable &t = ptab[kind];
+    if (!t.n_ids || r >= nres || o == 0 || o > t.n_ids || now < 0 || !out) return SGA_EINVAL;
     if (!d_view.p || d_view.n < 24) d_view.alloc(24);
-    hipLaunchKernelGGL(k_ofind, dim3(1), dim3(64), 0, stream, ostate(), r, o, (uint32_t *)d_view.p);
+    hipLaunchKernelGGL(k_ofind, dim3(1), dim3(64), 0, stream, pstate().t[kind], r, o, (uint32_t *)d_view.p);
     SGA_HIP_CHECK(hipGetLastError());
-    uint32_t q = kOriginNone;
+    uint32_t q = kPairNone;
     SGA_HIP_CHECK(hipMemcpyAsync(&q, d_view.p, 4, hipMemcpyDeviceToHost, stream));
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
-    if (q == kOriginNone) return SGA_ENOENT;  // getOriginCountMap().get(origin) == null
-    return query_at(d_onode.p, q, now, out);
+    // getOriginCountMap().get(origin) == null / NodeSelectorSlot's map has no DefaultNode for the context
+    if (q == kPairNone) return SGA_ENOENT;
+    return query_at(t.node.p, q, now, out);
 }
 
-int FlowEngine::origin_nodes_of(uint32_t r, uint32_t *origins, size_t cap, size_t *n) {
-    if (!n_origins || r >= nres || !n || (cap && !origins)) return SGA_EINVAL;
-    const uint32_t dcap = (uint32_t)std::min<size_t>(cap, n_origins);
+int FlowEngine::pair_nodes_of(int kind, uint32_t r, uint32_t *ids, size_t cap, size_t *n) {
+    const PairTable &t = ptab[kind];
+    if (!t.n_ids || r >= nres || !n || (cap && !ids)) return SGA_EINVAL;
+    const uint32_t dcap = (uint32_t)std::min<size_t>(cap, t.n_ids);
     if (d_olist.n < (size_t)dcap + 1) d_olist.alloc((size_t)dcap + 1);
     SGA_HIP_CHECK(hipMemsetAsync(d_olist.p, 0, 4, stream));
-    hipLaunchKernelGGL(k_onodes, dim3((oslots + kT - 1) / kT), dim3(kT), 0, stream, ostate(), r, d_olist.p + 1, dcap,
-                       d_olist.p);
+    hipLaunchKernelGGL(k_onodes, dim3((t.slots + kT - 1) / kT), dim3(kT), 0, stream, pstate().t[kind], r, d_olist.p + 1,
+                       dcap, d_olist.p);
     SGA_HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> got((size_t)dcap + 1);
     SGA_HIP_CHECK(hipMemcpyAsync(got.data(), d_olist.p, got.size() * 4, hipMemcpyDeviceToHost, stream));
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
     const size_t cnt = got[0];
-    for (size_t k = 0; k < std::min<size_t>(cnt, dcap); ++k) origins[k] = got[k + 1];
+    for (size_t k = 0; k < std::min<size_t>(cnt, dcap); ++k) ids[k] = got[k + 1];
     *n = std::min(cnt, cap);
     return cnt > cap ? SGA_ERANGE : 0;
 }

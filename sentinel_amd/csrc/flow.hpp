@@ -52,7 +52,8 @@ struct FlowRuleDev {    // one rater (TrafficShapingController) + its FlowRule f
     int32_t cslot;
     // FlowRule.strategy (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116): 0 =
     // DIRECT, the rater reads the resource's own node; otherwise RELATE, refResource's dense id + 1 -- nres + 1
-    // for a refResource that is no resource of the engine (its ClusterNode never exists: the rule passes)
+    // for a refResource that is no resource of the engine (its ClusterNode never exists: the rule passes), and for
+    // a rule whose limitApp or CHAIN context no event can carry.  A CHAIN rule's context is not here: PairCtx::rule_ctx
     uint32_t rel;
 };
 
@@ -130,33 +131,49 @@ struct SysDev {
     double cur_load, cur_cpu;
 };
 
-// Origin nodes (sga_flow_set_origins): one StatisticNode per (resource, origin) pair, created at the pair's
-// first entry (ClusterBuilderSlot.java:104-107) and counted by StatisticSlot next to the resource's ClusterNode
-// (StatisticSlot.java:81-84, 101-104, 123-125, 160-161).  An open-addressing table maps the pair to its node
-// record: key[h] = (resource + 1) << 32 | origin (0: empty; bit 63: a slot a refused chunk left without a
+// Pair nodes: one StatisticNode per (resource, origin) pair (sga_flow_set_origins) and one per (resource,
+// context) pair (sga_flow_set_contexts), two instances of one table behind the same kernels.
+// Origin nodes are created at the pair's first entry (ClusterBuilderSlot.java:104-107) and counted by
+// StatisticSlot next to the resource's ClusterNode (StatisticSlot.java:81-84, 101-104, 123-125, 160-161).
+// A context's DefaultNode is created by NodeSelectorSlot.entry (NodeSelectorSlot.java:158-177), ahead of
+// ClusterBuilderSlot and every check, and receives the same adds: DefaultNode's overrides (addPassRequest,
+// increaseBlockQps, increaseExceptionQps, addRtAndSuccess, increaseThreadNum, decreaseThreadNum) count on the
+// DefaultNode and on the ClusterNode.  An open-addressing table maps the pair to its node
+// record: key[h] = (resource + 1) << 32 | id (0: empty; bit 63: a slot a refused chunk left without a
 // record, matched by nobody), idx[h] = the record, born[h] = the event sequence of the pair's first kind 0 / 2 /
 // 3 event (~0: reserved by a refused chunk, not created).
-struct OriginState {
-    int64_t *node;             // max_nodes records of kNodeWords words, initialised like a resource's node
+struct PairState {
+    int64_t *node;             // max_nodes records of kNodeWords words, initialised like a resource's node;
+                               // null: this kind of pair is not registered
     unsigned long long *key, *born;
     uint32_t *idx;
-    uint32_t *ctl;             // [0] records handed out [1] this chunk's error bits (kOriginFull, kOriginBadId)
-                               // [2] this chunk's long segments
-    uint32_t mask, max_nodes, n_origins;
+    uint32_t *cnt;             // records handed out
+    uint32_t mask, max_nodes, n_ids;
 };
-constexpr uint32_t kOriginNone = 0xFFFFFFFFu;
-constexpr unsigned long long kOriginDead = 1ull << 63, kOriginUnborn = ~0ull;
-constexpr uint32_t kOriginFull = 1, kOriginBadId = 2;
-// What the arrival-order replay of an origin-ruled resource needs of the chunk (FlowState::octx; device memory,
-// rewritten per chunk): a resource with a FlowRule whose limitApp is an origin or "other" is decided in arrival
-// order as a RELATE group of its own, the rule's controller reading the origin node
-// (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:136-166).
-struct OriginCtx {
-    OriginState os;
-    const uint32_t *origin;    // per event (null: every event has origin 0)
-    const uint32_t *oslot;     // per event: the claim pass's table slot
+constexpr int kPairOrigin = 0, kPairContext = 1, kPairKinds = 2;
+constexpr uint32_t kPairNone = 0xFFFFFFFFu;
+constexpr unsigned long long kPairDead = 1ull << 63, kPairUnborn = ~0ull;
+constexpr uint32_t kPairFull = 1, kPairBadId = 2;
+// Both tables as the pair-node kernels see them.  The statistics pass sorts by one key over both: an origin
+// record q sorts under q, a context record q under base1 + q (base1 = the origin table's records, 0 without
+// one), an element without a node under total.
+struct PairTabs {
+    PairState t[kPairKinds];
+    uint32_t *ctl;             // [0] this chunk's error bits (kPairFull, kPairBadId) [1] its long segments
+    uint32_t base1, total;
+};
+// What the arrival-order replay of a pair-ruled resource needs of the chunk (FlowState::octx, the pair-node
+// state pointer; device memory, rewritten per chunk): a resource with a FlowRule whose limitApp is an origin or
+// "other", or whose strategy is CHAIN, is decided in arrival order as a RELATE group of its own, the rule's
+// controller reading the origin node or the context's DefaultNode
+// (FlowRuleChecker.selectNodeByRequesterAndStrategy, FlowRuleChecker.java:96-116, 136-166).
+struct PairCtx {
+    PairTabs pt;
+    const uint32_t *id[kPairKinds];    // per event (null: every event has id 0)
+    const uint32_t *slot[kPairKinds];  // per event: the claim pass's table slot
     const uint32_t *rule_lim;  // per rule (FlowState::rules order): SGA_LIMIT_*
-    const uint8_t *oruled;     // per resource: origin-ruled
+    const uint32_t *rule_ctx;  // per rule: a CHAIN rule's context id (refResource), 0 for any other strategy
+    const uint8_t *oruled;     // per resource: pair-ruled
     uint64_t seq_base;
 };
 
@@ -206,7 +223,7 @@ struct FlowState {
     uint32_t *lneed;             // count pass input: the batch's events with a key absent at its start ([2] of lru_ctl)
     uint32_t nprid, ntslot;      // parameter-rule ids, thread-map owner slots
     uint64_t seq_base;           // event sequence of the batch's first event
-    const OriginCtx *octx;       // null unless the loaded FlowRules hold one limited to an origin or "other"
+    const PairCtx *octx;         // null unless the loaded FlowRules hold one limited to an origin or "other", or a CHAIN one
 };
 constexpr uint32_t kLruThread = 1u << 31;
 
@@ -376,15 +393,16 @@ struct FlowEngine {
     uint64_t cluster_resolved_gen = ~0ull;
     int resolve_cluster(const std::function<int32_t(int64_t)> &slot_of_flow, uint64_t gen);
     int set_resources(uint32_t n);
-    // limit_app (sga_load_flow_rules_origin): null = every rule's limitApp is "default"
-    int load_flow_rules(const sga_flow_rule *r, size_t n, const uint32_t *limit_app = nullptr);
+    // limit_app (sga_load_flow_rules_origin / _ctx): null = every rule's limitApp is "default"; chain
+    // (sga_load_flow_rules_ctx): strategy 2 is valid, ref_resource its context id
+    int load_flow_rules(const sga_flow_rule *r, size_t n, const uint32_t *limit_app = nullptr, bool chain = false);
     int load_param_rules(const sga_param_rule *r, size_t n);
     int load_degrade_rules(const sga_degrade_rule *r, size_t n);
     void upload_res();
     int submit(const uint8_t *kind, const uint32_t *resource, const int64_t *ts, const int32_t *acquire,
                const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
                int32_t *wait_ms, const uint64_t *pvals = nullptr, size_t npvals = 0,
-               const uint32_t *origin = nullptr);
+               const uint32_t *origin = nullptr, const uint32_t *context = nullptr);
     FlowScratch special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
                                 const uint64_t *d_param_in, const uint64_t *d_pvals, const uint32_t *d_resource_in);
     DevBuf<uint64_t> d_pvals;  // values of Collection / array arguments (SGA_EV_PARAM_LIST)
@@ -398,37 +416,48 @@ struct FlowEngine {
     int submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire, const uint8_t *flags,
                      const int64_t *rt, const uint64_t *param, const uint32_t *ts_off, int64_t lo, uint32_t m,
                      int8_t *decision, int32_t *wait_ms, const uint64_t *pvals, size_t npvals,
-                     const uint32_t *origin = nullptr);
+                     const uint32_t *origin = nullptr, const uint32_t *context = nullptr);
     int submit_device(const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base, const uint32_t *d_ts_off,
                       const int32_t *d_acquire, const uint8_t *d_flags, const int64_t *d_rt_in,
                       const uint64_t *d_param_in, size_t n, const uint64_t *d_param_values, size_t n_values,
-                      int8_t *d_decision, int32_t *d_wait, hipStream_t s, const uint32_t *d_origin = nullptr);
-    // caller origins (OriginState): off until set_origins, and for every call that passes no origin array
-    uint32_t n_origins = 0, max_onodes = 0, oslots = 0;
-    DevBuf<int64_t> d_onode;
-    DevBuf<unsigned long long> d_okey, d_oborn;
-    DevBuf<uint32_t> d_oidx, d_octl, d_origin, d_oslot, d_olong;
-    // FlowRules limited to an origin or "other" (load_flow_rules): each rule's limitApp, the origin-ruled
-    // resources, and the chunk's OriginCtx
-    std::vector<uint32_t> h_rule_lim;
-    DevBuf<uint32_t> d_rule_lim;
+                      int8_t *d_decision, int32_t *d_wait, hipStream_t s, const uint32_t *d_origin = nullptr,
+                      const uint32_t *d_context = nullptr);
+    // pair nodes (PairState): a kind is off until set_pairs, and for every call that passes no id array of it
+    struct PairTable {
+        uint32_t n_ids = 0, max_nodes = 0, slots = 0;
+        DevBuf<int64_t> node;
+        DevBuf<unsigned long long> key, born;
+        DevBuf<uint32_t> idx, ids, slot;  // ids: the host entries' copy of the chunk's array
+    } ptab[kPairKinds];
+    DevBuf<uint32_t> d_pctl;   // [0] error bits [1] long segments [2 + kind] records handed out
+    DevBuf<uint32_t> d_olong;
+    // the statistics pass of a chunk that carries both arrays sorts two elements per event: buffers of its own,
+    // twice the pipeline's (allocated once both kinds are registered)
+    DevBuf<uint32_t> d_pkeys[2], d_phist[2], d_ppart;
+    DevBuf<Payload> d_ppay[2];
+    // FlowRules limited to an origin or "other", or of strategy CHAIN (load_flow_rules): each rule's limitApp and
+    // context, the pair-ruled resources, and the chunk's PairCtx
+    std::vector<uint32_t> h_rule_lim, h_rule_ctx;
+    DevBuf<uint32_t> d_rule_lim, d_rule_ctx;
     DevBuf<uint8_t> d_oruled;
-    DevBuf<OriginCtx> d_octx;
-    DevBuf<uint32_t> d_olist;  // origin_nodes_of: [0] count, then the ids
-    bool has_origin_rules = false;
-    void origin_ctx(const uint32_t *origin, hipStream_t s);  // before a chunk's decisions
-    int set_origins(uint32_t n, uint32_t max_nodes);
-    OriginState ostate() const;
+    DevBuf<PairCtx> d_octx;
+    DevBuf<uint32_t> d_olist;  // pair_nodes_of: [0] count, then the ids
+    bool has_pair_rules = false;
+    // before a chunk's decisions (ids[k] null: every event has id 0)
+    void pair_ctx(const uint32_t *const ids[kPairKinds], hipStream_t s);
+    int set_pairs(int kind, uint32_t n, uint32_t max_nodes);
+    PairTabs pstate() const;
     // the claim pass of a chunk (ahead of every check): the chunk's pairs find or claim their records.  Host
-    // entry (gate null): waits, SGA_ENOMEM when the table is full -- the chunk's claims are then taken back
-    int origin_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin, uint32_t m, uint32_t *gate,
-                     hipStream_t s);
+    // entry (gate null): waits, SGA_ENOMEM when a table is full -- the chunk's claims are then taken back
+    int pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds], uint32_t m,
+                   uint32_t *gate, hipStream_t s);
     // the statistics pass of a chunk, after its decisions (seq: one lane in arrival order, small chunks)
-    void origin_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin, const uint32_t *ts_off,
-                      int64_t ts_base, const int32_t *acquire, const uint8_t *flags, const int64_t *rt,
-                      const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq, hipStream_t s);
-    int query_origin(uint32_t resource, uint32_t origin, int64_t now, sga_node_view *out);
-    int origin_nodes_of(uint32_t resource, uint32_t *origins, size_t cap, size_t *n);
+    void pair_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
+                    const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
+                    const int64_t *rt, const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq,
+                    hipStream_t s);
+    int query_pair(int kind, uint32_t resource, uint32_t id, int64_t now, sga_node_view *out);
+    int pair_nodes_of(int kind, uint32_t resource, uint32_t *ids, size_t cap, size_t *n);
     int device_status();  // sticky error of the device entry since the last call (host wait)
     int ensure_scratch();
     DevBuf<uint32_t> d_gate;  // [0] gate word of the running chunk, [1] sticky error bits

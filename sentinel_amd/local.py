@@ -12,6 +12,9 @@ Same names and argument meaning as the Java API the engine replaces:
   ClusterNode statistics          CORE/node/StatisticNode.java:185-250 -> LocalSentinel.node
   ContextUtil.enter(name, origin) CORE/context/ContextUtil.java:116-160 -> the `origin` of entry / submit
   ClusterNode.getOriginCountMap   CORE/node/ClusterNode.java:116-118 -> LocalSentinel.origin_node / origin_nodes
+  ContextUtil.enter(name, ...)    the `context` of entry / submit; NodeSelectorSlot's DefaultNode per (resource,
+                                  context), CORE/slots/nodeselector/NodeSelectorSlot.java:158-177
+                                  -> LocalSentinel.default_node / default_nodes
 BlockException subclasses as in CORE/slots/block/BlockException.java and its subclasses.
 
 Every decision is computed by the HIP engine (libsentinel_amd.so).  The mocked
@@ -164,9 +167,10 @@ class Entry:
     """A passed entry; exit() records RT / success (StatisticSlot.exit) and breaker completion."""
 
     def __init__(self, owner: "LocalSentinel", rid: int, create_ts: int, count: int, param: Optional[int],
-                 wait_ms: int, inbound: bool = False, args=(), origin: str = ""):
+                 wait_ms: int, inbound: bool = False, args=(), origin: str = "", context: str = ""):
         self._owner = owner
         self.origin = origin
+        self.context = context
         self.args = tuple(args)
         self.inbound = inbound
         self.rid = rid
@@ -189,17 +193,20 @@ class Entry:
         word = encode_args(self.args, pvals)
         fl = (EV_ERROR if self.error else 0) | EV_ARGS | (EV_INBOUND if self.inbound else 0)
         self._owner.submit([KIND_EXIT], [self.rid], [now], [self.count], [fl], [now - self.create_timestamp],
-                           [word], pvals, origin=[self._owner.origin_id(self.origin)] if self.origin else None)
+                           [word], pvals, origin=[self._owner.origin_id(self.origin)] if self.origin else None,
+                           context=[self._owner.context_id(self.context)] if self.context else None)
 
 
 class LocalSentinel:
     """The local slot chain (StatisticSlot, ParamFlowSlot, FlowSlot, DegradeSlot) on one engine."""
 
     def __init__(self, engine: Engine, resources: Sequence[str], origins: Optional[Sequence[str]] = None,
-                 max_origin_nodes: int = 0):
+                 max_origin_nodes: int = 0, contexts: Optional[Sequence[str]] = None, max_context_nodes: int = 0):
         """origins: the caller names events may carry (ContextUtil.enter's origin), registered up front like
         the resources; None = no origin tracking.  max_origin_nodes sizes the engine's table of (resource,
-        origin) nodes (0: the engine's default)."""
+        origin) nodes (0: the engine's default).  contexts: the context names events may carry
+        (ContextUtil.enter's name), registered the same way and independently; None = no DefaultNodes, no CHAIN
+        rules.  max_context_nodes sizes the table of (resource, context) DefaultNodes."""
         self.engine = engine
         self.resources: List[str] = list(resources)
         self.ids: Dict[str, int] = {r: i for i, r in enumerate(self.resources)}
@@ -213,10 +220,24 @@ class LocalSentinel:
         for o in self.origins:  # the names FlowRule.limitApp reserves (AuthorityRuleChecker / filterOrigin)
             if o in (RuleConstant.LIMIT_APP_DEFAULT, RuleConstant.LIMIT_APP_OTHER) or not o:
                 raise ValueError(f"origin name {o!r} is reserved")
+        self.contexts: List[str] = list(contexts) if contexts else []
+        # context ids are 1-based: 0 is "no tracked context" (the default context, whose DefaultNodes nobody reads)
+        self.context_ids: Dict[str, int] = {c: i + 1 for i, c in enumerate(self.contexts)}
+        if len(self.context_ids) != len(self.contexts):
+            raise ValueError("duplicate context names")
+        if any(not c for c in self.contexts):
+            raise ValueError("context name '' is reserved")
         check(_lib.load().sga_flow_set_resources(engine.handle, len(self.resources)), engine.handle, "setResources")
         if self.origins:
             check(_lib.load().sga_flow_set_origins(engine.handle, len(self.origins), max_origin_nodes),
                   engine.handle, "setOrigins")
+        if self.contexts:
+            check(_lib.load().sga_flow_set_contexts(engine.handle, len(self.contexts), max_context_nodes),
+                  engine.handle, "setContexts")
+
+    def context_id(self, name: str) -> int:
+        """Dense id of a registered context; "" is 0 (no tracked context)."""
+        return self.context_ids[name] if name else 0
 
     def origin_id(self, name: str) -> int:
         """Dense id of a registered origin; "" is 0."""
@@ -226,10 +247,12 @@ class LocalSentinel:
         return self.ids[name]
 
     # ---- batched form: the engine's native interface
-    def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None):
+    def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None,
+               context=None):
         """Events in arrival order.  param_values: the values of Collection / array arguments
         (events flagged SGA_EV_PARAM_LIST = 16 carry param = offset << 32 | count into it).
-        origin: each event's origin id (origin_id; 0 = none), on a sentinel with registered origins."""
+        origin: each event's origin id (origin_id; 0 = none), on a sentinel with registered origins.
+        context: each event's context id (context_id; 0 = none), on a sentinel with registered contexts."""
         k = np.ascontiguousarray(kind, dtype=np.uint8)
         r = np.ascontiguousarray(resource, dtype=np.uint32)
         t = np.ascontiguousarray(ts, dtype=np.int64)
@@ -246,6 +269,19 @@ class LocalSentinel:
         dec = np.zeros(n, dtype=np.int8)
         wait = np.zeros(n, dtype=np.int32)
         vals = np.ascontiguousarray(param_values, dtype=np.uint64) if param_values is not None else None
+        if context is not None:
+            og = np.ascontiguousarray(origin, dtype=np.uint32) if origin is not None else None
+            cx = np.ascontiguousarray(context, dtype=np.uint32)
+            if len(cx) != n or (og is not None and len(og) != n):
+                raise ValueError("event arrays differ in length")
+            rc = _lib.load().sga_submit_events_ctx(
+                self.engine.handle, k.ctypes.data, r.ctypes.data, t.ctypes.data, a.ctypes.data,
+                f.ctypes.data if f is not None else None, rtv.ctypes.data if rtv is not None else None,
+                pv.ctypes.data if pv is not None else None, og.ctypes.data if og is not None else None,
+                cx.ctypes.data, n, vals.ctypes.data if vals is not None and len(vals) else None,
+                len(vals) if vals is not None else 0, dec.ctypes.data, wait.ctypes.data)
+            check(rc, self.engine.handle, "submitEvents")
+            return dec, wait
         if origin is not None:
             og = np.ascontiguousarray(origin, dtype=np.uint32)
             if len(og) != n:
@@ -311,20 +347,20 @@ class LocalSentinel:
         return int(d.value), int(w.value)
 
     def submit_device(self, kind, resource, ts_base, ts_off, acquire, flags=None, rt=None, param=None,
-                      param_values=None, decision=None, wait=None, stream=None, origin=None):
+                      param_values=None, decision=None, wait=None, stream=None, origin=None, context=None):
         """submit over device tensors (torch, on the engine's GPU), asynchronous on `stream` (torch stream or
         None = the engine stream): one chunk of at most max_batch events with timestamps ts_base + ts_off.
         Returns (decision int8, wait int32) device tensors; device_status() reports a chunk the device
         checks rejected (rc -EINVAL) or a full parameter map (rc -ENOMEM) as EngineError."""
         import torch
         n = kind.numel()
-        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param, origin) if v is not None):
+        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param, origin, context) if v is not None):
             if x.numel() != n or not x.is_cuda or not x.is_contiguous():
                 raise ValueError("event tensors must be contiguous device tensors of one length")
         want = {"kind": (kind, torch.uint8), "resource": (resource, torch.int32), "ts_off": (ts_off, torch.int32),
                 "acquire": (acquire, torch.int32), "flags": (flags, torch.uint8), "rt": (rt, torch.int64),
                 "param": (param, torch.int64), "param_values": (param_values, torch.int64),
-                "origin": (origin, torch.int32)}
+                "origin": (origin, torch.int32), "context": (context, torch.int32)}
         for name, (x, dt) in want.items():
             if x is not None and x.element_size() != torch.empty(0, dtype=dt).element_size():
                 raise ValueError(f"{name}: element size of {dt} expected")
@@ -333,6 +369,14 @@ class LocalSentinel:
         if wait is None:
             wait = torch.empty(n, dtype=torch.int32, device=kind.device)
         ptr = (lambda x: x.data_ptr() if x is not None else None)
+        if context is not None:  # context (and origin) ids per event; a full table: device_status, rc -ENOMEM
+            rc = _lib.load().sga_submit_events_ctx_device(
+                self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
+                acquire.data_ptr(), ptr(flags), ptr(rt), ptr(param), ptr(origin), context.data_ptr(), n,
+                ptr(param_values), param_values.numel() if param_values is not None else 0, decision.data_ptr(),
+                wait.data_ptr(), stream.cuda_stream if stream is not None else None)
+            check(rc, self.engine.handle, "submitEventsDevice")
+            return decision, wait
         if origin is not None:  # origin ids per event (a full origin table: device_status, rc -ENOMEM)
             rc = _lib.load().sga_submit_events_origin_device(
                 self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
@@ -355,9 +399,10 @@ class LocalSentinel:
 
     # ---- SphU-style single entry
     def entry(self, resource: str, now: int, batch_count: int = 1, prioritized: bool = False, args=(),
-              entry_type: str = "OUT", origin: str = "") -> Entry:
+              entry_type: str = "OUT", origin: str = "", context: str = "") -> Entry:
         """SphU.entry(resource, entryType, batchCount, args); entry_type "IN" marks inbound traffic; origin:
-        the caller the context was entered with (a registered origin name), kept by the Entry for its exit."""
+        the caller the context was entered with (a registered origin name), context: that context's name (a
+        registered context; "" = the default context, untracked), both kept by the Entry for its exit."""
         rid = self.ids[resource]
         inbound = entry_type == "IN"
         # the whole argument vector (SGA_EV_ARGS): ParamFlowSlot indexes args by each rule's paramIdx
@@ -365,13 +410,14 @@ class LocalSentinel:
         word = encode_args(tuple(args), pvals)
         fl = (EV_PRIORITIZED if prioritized else 0) | EV_ARGS | (EV_INBOUND if inbound else 0)
         dec, wait = self.submit([KIND_ENTRY], [rid], [now], [batch_count], [fl], None, [word], pvals,
-                                origin=[self.origin_id(origin)] if origin else None)
+                                origin=[self.origin_id(origin)] if origin else None,
+                                context=[self.context_id(context)] if context else None)
         d = int(dec[0])
         if d in _EXC:
             raise _EXC[d](resource)
         param = param_value(args[0]) if len(args) > 0 and args[0] is not None and \
             not isinstance(args[0], (list, tuple)) else None
-        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin)
+        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin, context)
 
     def node(self, resource, now: int) -> NodeView:
         """ClusterNode views; resource ENTRY_NODE (or TOTAL_IN_RESOURCE_NAME) is Constants.ENTRY_NODE."""
@@ -402,6 +448,27 @@ class LocalSentinel:
         check(_lib.load().sga_origin_nodes_of(self.engine.handle, rid, buf, len(self.origins), C.byref(n)),
               self.engine.handle, "originNodes")
         return [self.origins[i - 1] for i in sorted(buf[:n.value])]
+
+    def default_node(self, resource, context, now: int) -> Optional[NodeView]:
+        """The DefaultNode of the resource in the context (NodeSelectorSlot's map): its views, None while the
+        resource has not been entered in that context."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        cid = context if isinstance(context, int) else self.context_ids[context]
+        v = SgaNodeView()
+        rc = _lib.load().sga_query_context_node(self.engine.handle, rid, cid, now, C.byref(v))
+        if rc == _lib.SGA_ENOENT:
+            return None
+        check(rc, self.engine.handle, "defaultNode")
+        return NodeView(*[getattr(v, f) for f, _ in SgaNodeView._fields_])
+
+    def default_nodes(self, resource) -> List[str]:
+        """The contexts with a DefaultNode on the resource, sorted by id."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        buf = (C.c_uint32 * max(1, len(self.contexts)))()
+        n = C.c_size_t()
+        check(_lib.load().sga_context_nodes_of(self.engine.handle, rid, buf, len(self.contexts), C.byref(n)),
+              self.engine.handle, "defaultNodes")
+        return [self.contexts[i - 1] for i in sorted(buf[:n.value])]
 
     def metrics(self, now: int, cap: int = 1 << 16) -> List[MetricNode]:
         """MetricTimerListener.run (CORE/node/metric/MetricTimerListener.java:44-65): StatisticNode.metrics()
@@ -464,6 +531,9 @@ class FlowRuleManager:
         # then applies to that origin's entries, or "other" to the origins no rule of the resource names, and
         # reads the origin node); one without keeps the plain loader and its mapping
         oids = getattr(self.s, "origin_ids", None) or None
+        # one with registered contexts names a CHAIN rule's refResource, a context name, by id
+        # (sga_load_flow_rules_ctx: the rule then applies to that context's entries and reads their DefaultNode)
+        cids = getattr(self.s, "context_ids", None) or None
         lim = (C.c_uint32 * max(1, len(rules)))()
         for i, r in enumerate(rules):
             a = arr[i]
@@ -473,7 +543,8 @@ class FlowRuleManager:
             a.control_behavior = r.control_behavior
             a.warm_up_period_sec = r.warm_up_period_sec
             a.max_queueing_time_ms = r.max_queueing_time_ms
-            # CHAIN is not served by the engine (it refuses strategy 2 itself), nor a non-default limitApp on a
+            # CHAIN is not served on a sentinel without registered contexts (the plain loaders refuse strategy 2
+            # themselves), nor a non-default limitApp on a
             # sentinel without registered origins: rejected as invalid.  RELATE (FlowRuleChecker.java:96-116) names its refResource by dense
             # id -- SGA_REF_NONE for a name this sentinel has no resource for: its ClusterNode never exists, so
             # the rule never blocks; a blank refResource is invalid (FlowRuleUtil.checkStrategyField)
@@ -487,6 +558,12 @@ class FlowRuleManager:
                     a.strategy = -1
                 else:
                     a.ref_resource = self.s.ids.get(r.ref_resource, _lib.SGA_REF_NONE)
+            elif a.strategy == RuleConstant.STRATEGY_CHAIN and cids:
+                # an unregistered context name: no event can carry it (valid, never applies); blank: invalid
+                if r.ref_resource is None or not r.ref_resource.strip():
+                    a.strategy = -1
+                else:
+                    a.ref_resource = cids.get(r.ref_resource, _lib.SGA_CONTEXT_UNKNOWN)
             if r.cluster_mode:
                 cc = r.cluster_config
                 a.cluster_mode = 1
@@ -495,6 +572,10 @@ class FlowRuleManager:
                 a.cluster_sample_count = 0 if cc is None else cc.sample_count
                 a.cluster_window_ms = 0 if cc is None else cc.window_interval_ms
                 a.cluster_strategy = 0 if cc is None else cc.strategy
+        if cids:
+            return check(_lib.load().sga_load_flow_rules_ctx(self.s.engine.handle, arr, lim if oids else None,
+                                                             len(rules)),
+                         self.s.engine.handle, "FlowRuleManager.loadRules")
         if oids:
             return check(_lib.load().sga_load_flow_rules_origin(self.s.engine.handle, arr, lim, len(rules)),
                          self.s.engine.handle, "FlowRuleManager.loadRules")

@@ -55,7 +55,7 @@ class FlowRule:
     grade: int = RuleConstant.FLOW_GRADE_QPS
     limit_app: str = RuleConstant.LIMIT_APP_DEFAULT
     strategy: int = RuleConstant.STRATEGY_DIRECT
-    ref_resource: Optional[str] = None  # FlowRule.refResource (STRATEGY_RELATE)
+    ref_resource: Optional[str] = None  # FlowRule.refResource (STRATEGY_RELATE: a resource; STRATEGY_CHAIN: a context)
     control_behavior: int = RuleConstant.CONTROL_BEHAVIOR_DEFAULT
     warm_up_period_sec: int = 10
     max_queueing_time_ms: int = 500
