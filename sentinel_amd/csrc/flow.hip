@@ -7040,10 +7040,25 @@ static bool pseg_on() {
     return !off;
 }
 
+#ifdef SGA_TEST_HOOKS
+// The test-only build's record of the last host chunk (FlowEngine::submit): which scratch its dispatch counts
+// are in, and what the host code decided about it.  Read back by sga_test_local_dispatch.
+struct HookChunk {
+    const uint32_t *counters = nullptr, *cbt_ctl = nullptr;
+    hipStream_t stream = nullptr;
+    bool small = false, tiled = false;  // k_lsmall took the chunk; the k_cbt_* kernels were launched
+    uint32_t events = 0, chunks = 0;    // the chunk's events; chunks since the last read-back
+};
+static HookChunk g_hook_chunk;
+#endif
+
 void FlowEngine::launch_pseg(const FlowState &st, const FlowScratch &g, const Payload *pay, const uint32_t *keys,
                              int64_t ts_base, const int64_t *rt, const uint64_t *param, int8_t *decision,
                              int32_t *wait_ms, uint32_t m, hipStream_t s) {
     if (!g.pseg || m == 0) return;
+#ifdef SGA_TEST_HOOKS
+    g_hook_chunk.tiled = !h_cbs.empty() && m >= kCbTileMin;
+#endif
     FlowScratch gs = g;
     const uint64_t none = ((uint64_t)st.tmask + 1) << 32;  // after every map slot
     int sbits = 1;
@@ -7443,6 +7458,15 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         for (size_t i = 0; any_list && i < m && !has_list; ++i) has_list = is_list(b + i);
         for (size_t i = 0; i < m; ++i)
             if (kind[b + i] > SGA_KIND_REVOKE) return SGA_EINVAL;
+#ifdef SGA_TEST_HOOKS
+        g_hook_chunk.counters = sc.counters;
+        g_hook_chunk.cbt_ctl = sc.cbt_ctl;
+        g_hook_chunk.stream = stream;
+        g_hook_chunk.small = m <= small_max && !(has_in && sys.check) && (!has_list || npvals <= kSmallWords);
+        g_hook_chunk.tiled = false;
+        g_hook_chunk.events = (uint32_t)m;
+        ++g_hook_chunk.chunks;
+#endif
         if (m <= small_max && !(has_in && sys.check) && (!has_list || npvals <= kSmallWords)) {
             if (const int rc = submit_small(kind + b, resource + b, acquire + b, flags ? flags + b : nullptr,
                                             rt ? rt + b : nullptr, param ? param + b : nullptr, off.data(), lo,
@@ -7999,3 +8023,29 @@ int FlowEngine::cb_state(uint32_t r, uint32_t k) {
 }
 
 }  // namespace sga
+
+#ifdef SGA_TEST_HOOKS
+// Test-only build: how the last host chunk of this process (FlowEngine::submit) was dispatched.
+//   out[0] flows sent to k_lheavy       out[1] flows sent to k_lwave          out[2] LRU flows (k_llru)
+//   out[3] per-segment flows            out[4] segments (k_pseg_heads)        out[5] long segments (k_pseg_long)
+//   out[6] breaker flows (k_cb_flows)   out[7] RELATE groups sent to k_lgroup out[8] tiled breaker flows (k_cbt_*)
+//   out[9] 1: k_lsmall replayed the chunk (the counts above are zero then)    out[10] the chunk's events
+//   out[11] host chunks since the last call
+// Returns the number of words written, or -1 (no chunk yet, n < 12, or the copy failed).  The product library
+// does not have this symbol.
+extern "C" int sga_test_local_dispatch(uint32_t *out, size_t n) {
+    sga::HookChunk &h = sga::g_hook_chunk;
+    if (!out || n < 12 || !h.counters) return -1;
+    uint32_t c[16] = {0}, ctl[2] = {0, 0};
+    if (!h.small) {
+        if (hipMemcpyAsync(c, h.counters, 64, hipMemcpyDeviceToHost, h.stream) != hipSuccess) return -1;
+        if (h.tiled && hipMemcpyAsync(ctl, h.cbt_ctl, 8, hipMemcpyDeviceToHost, h.stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(h.stream) != hipSuccess) return -1;
+    }
+    const uint32_t v[12] = {c[8], c[9], c[10], c[11], c[12], c[14], c[13], c[15], ctl[0], h.small ? 1u : 0u,
+                            h.events, h.chunks};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    h.chunks = 0;
+    return 12;
+}
+#endif
