@@ -959,6 +959,35 @@ constexpr int kFzLong = 512;    // longer runs listed for the results phase (one
                                 // sends further runs to their flows lane as well
 constexpr uint32_t kFzHuge = 2048;  // listed runs answered by the whole workgroup (no SHOULD_WAIT among them)
 
+// Test-only build (SGA_TEST_HOOKS, libsentinel_amd_testhooks.so): how the last batch was dispatched, counted
+// with plain atomic adds and read back by sga_test_cluster_dispatch.  The product build has none of it.
+#ifdef SGA_TEST_HOOKS
+enum : int {
+    CD_CHUNK = 0,   // k_cold_fused<chunk> launches
+    CD_BIN,         // k_cold_fused<bin> launches
+    CD_BIN_LDS,     // bins ordered into the LDS image
+    CD_BIN_GLOBAL,  // bins ordered in global memory
+    CD_DIRECT,      // closed-form runs of at most kFzDirect requests, answered by their flows lane
+    CD_WAVE,        // listed runs answered by one wave
+    CD_WG,          // listed runs answered by the whole workgroup
+    CD_REPLAY,      // runs replayed per request
+    CD_LISTFULL,    // longer closed-form runs sent back to their lane by a full list
+    CD_GLOBAL_REC,  // run records read from the global run arrays
+    CD_CONT,        // rules continued past their chunk
+    CD_GALLOP,      // ... of which galloped (no end within one chunk ahead)
+    CD_PSEARCH,     // prio_before searches (more than four prioritized requests in the run)
+    CD_COUNTER,     // rules taken from the workgroup counter
+    CD_DROPPED,     // next-hot-set candidates dropped
+    CD_HOTRUN,      // hot runs
+    CD_HOTCW,       // hot runs with cw > 0
+    CD_N
+};
+__device__ uint32_t g_cd[CD_N];
+#define CD_COUNT(k) atomicAdd(&g_cd[k], 1u)
+#else
+#define CD_COUNT(k) ((void)0)
+#endif
+
 // Profiling only (SGA_FZ_DEBUG bit 16): per-phase cycles of k_cold_fused summed over workgroups.
 __device__ unsigned long long g_fz_phase[8];
 __device__ __forceinline__ void fz_mark(int dbg, int ph, unsigned long long &t) {
@@ -1166,6 +1195,8 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
     // prioritized index (relative to h0 in bin mode), acquire count | bucket delta << 8
     __shared__ RlT rl_buf[4 * kRl];
     RlT *rl_n = rl_buf, *rl_cp = rl_buf + kRl, *rl_p0 = rl_buf + 2 * kRl, *rl_ab = rl_buf + 3 * kRl;
+    // (only a bin can fill the list: a chunk-form workgroup owns 2048 elements of whole rules and one continuing
+    // rule of at most kBdEsc closed-form runs, so fewer than kFzLong runs of more than kFzDirect requests)
     __shared__ uint32_t s_long[kFzLong];  // closed-form runs the flows lanes left to the results phase (heads)
     __shared__ uint32_t s_nlong, s_huge;
     __shared__ FAgg wtot[kFzThreads / 64];
@@ -1185,9 +1216,11 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
     // element p: an LDS read (ds_read) when the bin is in LDS -- a flat pointer into LDS would make every
     // element read wait for all outstanding global stores as well
     uint32_t h0, E;
+    if (blockIdx.x == 0 && threadIdx.x == 0) CD_COUNT(kBin ? CD_BIN : CD_CHUNK);
     if constexpr (kMode == kFzBin) {
         const uint32_t B0 = sc.pstart[blockIdx.x], B1 = sc.pstart[blockIdx.x + 1];
         if (B0 >= B1) return;
+        if (threadIdx.x == 0) CD_COUNT(B1 - B0 <= (uint32_t)kBinLds ? CD_BIN_LDS : CD_BIN_GLOBAL);
         unsigned long long ot = 0;
         fz_mark(dbg, 0, ot);
         in_lds = B1 - B0 <= (uint32_t)kBinLds;
@@ -1232,6 +1265,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         if (el_slot(el[c1]) == ls) {  // uniform
             __syncthreads();
             if (threadIdx.x == 0) s_E = 0xFFFFFFFFu;
+            if (threadIdx.x == 0) CD_COUNT(CD_CONT);
             __syncthreads();
             // one chunk ahead with the whole workgroup, then (long rules only) gallop + bisect
             for (uint32_t p = c1 + threadIdx.x; p < min(n, c1 + kFzChunk); p += kFzThreads)
@@ -1241,6 +1275,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
                 }
             __syncthreads();
             if (threadIdx.x == 0 && s_E == 0xFFFFFFFFu) {
+                CD_COUNT(CD_GALLOP);
                 uint32_t lo = min(n, c1 + kFzChunk), step = kFzChunk;  // slot(el[lo - 1]) == ls
                 uint32_t hi = lo;
                 while (true) {  // gallop: first probe with slot != ls (or n)
@@ -1384,6 +1419,8 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
             if (k < (uint32_t)kFzThreads) {
                 s_cand[2 * k] = s;
                 s_cand[2 * k + 1] = r1 - r;
+            } else {
+                CD_COUNT(CD_DROPPED);
             }
         }
         if (st.uni_S) {
@@ -1419,6 +1456,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
             ri.a = (int32_t)(ab & 0xFFu);
             ri.bd = ab >> 8;
         } else {
+            CD_COUNT(CD_GLOBAL_REC);
             ri.n = sc.run_start[r];
             ri.cp_tot = sc.run_cp[r];
             ri.p0 = sc.run_p0[r];
@@ -1437,6 +1475,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
                 for (int u = 0; u < 4; ++u) c += ((uint32_t)u < ri.cp_tot && pv[u] < ri.j0 + k) ? 1u : 0u;
                 return c;
             }
+            CD_COUNT(CD_PSEARCH);
             uint32_t lo = 0, hi = ri.cp_tot;
             while (lo < hi) {
                 const uint32_t m = (lo + hi) >> 1;
@@ -1452,6 +1491,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         bool fast = run_compact(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro, wide);
         if (wide) fast = run_wide(st, P, R, thr, hdr_thr, qbase, ri, prio_before, ro);
         if (!fast) {
+            CD_COUNT(CD_REPLAY);
             for (uint32_t j = r; j < r + ri.n; ++j) {
                 const uint32_t i = el_idx(EL(j));
                 const int64_t t = ts_base + (int64_t)in.ts_at(i);
@@ -1470,7 +1510,10 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
                 if (ri.n >= kFzHuge && ro.cw == 0) s_huge = 1u;
             } else {
                 direct = true;
+                CD_COUNT(CD_LISTFULL);
             }
+        } else if (direct) {
+            CD_COUNT(CD_DIRECT);
         }
         if (direct) {
             // the run's elements in chunks of 8, loaded together at clamped positions, decided as the results
@@ -1505,6 +1548,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         if (r >= r1) {
             f = atomicAdd(&s_next, 1u);
             live = f < nf;
+            if (live) CD_COUNT(CD_COUNTER);
             if (live) take_rule();
         }
     }
@@ -1534,6 +1578,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         const RunOut ro = sc.run_out[hp];
         const uint32_t n = run_len(hp);
         if (ro.cw != 0 || n < kFzHuge) continue;
+        if (threadIdx.x == 0) CD_COUNT(CD_WG);
         constexpr uint32_t kStep = kFzThreads * 8;
         for (uint32_t c0 = 0; c0 < n; c0 += kStep) {
             uint64_t x[8];
@@ -1560,6 +1605,7 @@ __global__ __launch_bounds__(kFzThreads) __attribute__((amdgpu_waves_per_eu(3)))
         const uint32_t hp = s_long[k];
         const RunOut ro = sc.run_out[hp];
         if (ro.cw == 0 && run_len(hp) >= kFzHuge) continue;
+        if (lane == 0) CD_COUNT(CD_WAVE);
         const uint32_t n = (hp - h0 < rl_cap) ? (uint32_t)rl_n[hp - h0] : sc.run_start[hp];
         uint32_t kp0 = 0;
         for (uint32_t c0 = 0; c0 < n; c0 += 64) {
@@ -2816,6 +2862,8 @@ __global__ __launch_bounds__(kThreads) void k_hot_flows(ClusterState st, BatchSc
             atomicAdd(&sc.counters[CTL_HOTERR], 1u);
         }
         if (lane == 0) {
+            CD_COUNT(CD_HOTRUN);
+            if (cw > 0) CD_COUNT(CD_HOTCW);
             HotRun r{};
             r.s0 = s0;
             r.thr = thr;
@@ -3823,6 +3871,17 @@ static int fz_debug() {
     return v;
 }
 
+// Test-only build: the dispatch counts start at zero for every batch.
+static void test_dispatch_reset(hipStream_t s) {
+#ifdef SGA_TEST_HOOKS
+    void *p = nullptr;
+    SGA_HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_cd)));
+    SGA_HIP_CHECK(hipMemsetAsync(p, 0, sizeof(uint32_t) * CD_N, s));
+#else
+    (void)s;
+#endif
+}
+
 void batch_scratch_release(BatchScratch &sc) {
     if (sc.side) (void)hipStreamDestroy(sc.side);
     if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork);
@@ -3837,15 +3896,16 @@ void batch_scratch_release(BatchScratch &sc) {
 
 
 // Cold stage of a large batch over the sorted elements: runs, flows and results in one kernel.
-// Partitioned (sc.part_lb > 0, hot path): one workgroup per slot bin, el = the partition output, each bin
-// ordered into the other element buffer first.
+// Partitioned (part_lb > 0, hot path only): one workgroup per slot bin, el = the partition output, each bin
+// ordered into the other element buffer first.  The form is the caller's choice: sc.part_lb is what the last
+// hot-path batch's key passes chose and says nothing about a sorted batch, so the sort path passes 0.
 static void cold_stage(const ClusterState &st, BatchScratch &sc, const uint64_t *el, uint32_t n, const uint32_t *dn,
                        uint32_t invalid_key, const ReqIn &in, int64_t ts_base, int simple, uint32_t hot_min,
-                       uint64_t *out, hipStream_t s) {
-    if (sc.part_lb) {
+                       uint64_t *out, hipStream_t s, int part_lb) {
+    if (part_lb) {
         uint64_t *es = el == sc.el[0] ? sc.el[1] : sc.el[0];
         hipLaunchKernelGGL(k_cold_fused_t<kFzBin>, dim3(kPartBins), dim3(kFzThreads), 0, s, st, sc, el, n, dn,
-                           invalid_key, in, ts_base, simple, hot_min, out, fz_debug(), es, sc.part_lb);
+                           invalid_key, in, ts_base, simple, hot_min, out, fz_debug(), es, part_lb);
         return;
     }
     hipLaunchKernelGGL(k_cold_fused, dim3((n + kFzChunk - 1) / kFzChunk), dim3(kFzThreads), 0, s, st, sc, el, n, dn,
@@ -4130,7 +4190,8 @@ static void hot_side(const ClusterState &st, BatchScratch &sc, int64_t ts_base, 
 static void cold_stage_and_next(const ClusterState &st, BatchScratch &sc, const ReqIn &in, int64_t ts_base,
                                 uint32_t n, uint64_t *out, hipStream_t s) {
     const uint32_t hot_min = std::max<uint32_t>(sc.hot_min, 1);
-    cold_stage(st, sc, sc.el_sorted, n, sc.counters + CTL_NCOLD, st.nslots, in, ts_base, 0, hot_min, out, s);
+    cold_stage(st, sc, sc.el_sorted, n, sc.counters + CTL_NCOLD, st.nslots, in, ts_base, 0, hot_min, out, s,
+               sc.part_lb);
     if (fz_debug()) {  // profiling only: k_cold_fused phase cycles per workgroup
         unsigned long long ph[8];
         SGA_HIP_CHECK(hipMemcpyFromSymbolAsync(ph, HIP_SYMBOL(g_fz_phase), sizeof(ph), 0, hipMemcpyDeviceToHost, s));
@@ -4186,6 +4247,7 @@ void cluster_classify_hot(const ClusterState &st, BatchScratch &sc, const int64_
                           hipStream_t s) {
     const bool clean = sc.counters_clean != 0;
     sc.counters_clean = 0;
+    test_dispatch_reset(s);
     ReqIn in;
     in.flow = flow_id;
     in.acq = acquire;
@@ -4225,6 +4287,7 @@ void cluster_decide_batch(const ClusterState &st, BatchScratch &sc, const int64_
                           const uint8_t *prio, int64_t ts_base, const uint32_t *ts_off, uint32_t n, int simple,
                           void *out_v, hipStream_t s, const LimiterPass *lims, int nlims) {
     if (n == 0) return;
+    test_dispatch_reset(s);
     ReqIn in;
     in.flow = flow_id;
     in.acq = acquire;
@@ -4268,7 +4331,7 @@ void cluster_decide_batch(const ClusterState &st, BatchScratch &sc, const int64_
     if (!simple) apply_limiters(st.param, sc, sc.el[0], n, invalid_key, ts_base, ts_off, out, lims, nlims, s);
     const int np = radix_sort_u64(sc.el[0], sc.el[1], n, kSlotShift, bits, sc.radix, s, !limited);
     if (np != npass) throw HipError("radix pass count mismatch", __FILE__, __LINE__);
-    cold_stage(st, sc, el, n, nullptr, invalid_key, in, ts_base, simple, 0xFFFFFFFFu, out, s);
+    cold_stage(st, sc, el, n, nullptr, invalid_key, in, ts_base, simple, 0xFFFFFFFFu, out, s, 0);
 }
 
 // packed requests -> the four arrays (the paths other than the hot one read those)
@@ -4288,6 +4351,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack(const uint32_t *__restrict_
 void cluster_decide_batch_packed(const ClusterState &st, BatchScratch &sc, const uint32_t *pk, int64_t ts_base,
                                  uint32_t n, void *out_v, hipStream_t s, const LimiterPass *lims, int nlims) {
     if (n == 0) return;
+    test_dispatch_reset(s);
     const bool small = n <= std::min<uint32_t>(sc.small_max, kSmall) && nlims == 0 && !radix64_lookback();
     if (!small && cluster_hot_eligible(st, sc, n, 0, nlims)) {
         const bool clean = sc.counters_clean != 0;
@@ -4541,3 +4605,16 @@ void cluster_sync_rec_thr(const ClusterState &st, uint32_t n, hipStream_t s) {
 }
 
 }  // namespace sga
+
+#ifdef SGA_TEST_HOOKS
+// Test-only build: how the last cluster batch was dispatched (the CD_* counts, in their order).  Waits for the
+// device first.  Returns the number of words written, or -1 (n too small, or the copy failed).  The product
+// library does not have this symbol.
+extern "C" int sga_test_cluster_dispatch(uint32_t *out, size_t n) {
+    if (!out || n < (size_t)sga::CD_N) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sga::g_cd), sizeof(uint32_t) * sga::CD_N, 0, hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return (int)sga::CD_N;
+}
+#endif

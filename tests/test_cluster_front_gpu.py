@@ -124,8 +124,9 @@ def expected_hot_next(rules, fid, hot_min):
 @pytest.mark.parametrize("n", SHAPES)
 def test_front_shapes_match_oracle(n, hot_min):
     """Four consecutive batches per shape: one key workgroup, a short last segment, 66 segments (more than
-    the 64 stripes of the totals, and two partition groups with two segments in the second).  From the second batch on the hot path is
-    taken with no flag."""
+    the 64 stripes of the totals).  With 3,050 rules the cold elements are LSD-sorted, so no cold partition runs
+    here (tests/cluster_shapes.py group P has 65 segments over 30,000 rules: two partition groups).  From the
+    second batch on the hot path is taken with no flag."""
     from sentinel_amd import cluster
     rules = rule_list(DENSE_IDS)
     rng = np.random.default_rng(1000 + n + hot_min)
