@@ -713,6 +713,34 @@ int sga_query_context_node(sga_engine *e, uint32_t resource, uint32_t context, i
  * SGA_ERANGE when there are more. */
 int sga_context_nodes_of(sga_engine *e, uint32_t resource, uint32_t *contexts, size_t cap, size_t *n);
 
+/* ---- node views in bulk (new entry points only): what the command center's clusterNode, cnode, origin and
+ * systemStatus commands read ---- */
+#define SGA_NODES_RESOURCE 0 /* ClusterNodes (ClusterBuilderSlot.getClusterNodeMap) and Constants.ENTRY_NODE */
+#define SGA_NODES_ORIGIN   1 /* origin nodes (ClusterNode.getOriginCountMap) */
+#define SGA_NODES_CONTEXT  2 /* DefaultNodes */
+#define SGA_NODES_NOT_ZERO 1u /* keep the rows with total_pass + total_block > 0 (clusterNode?type=notZero) */
+typedef struct sga_node_row {
+    uint32_t resource, other;   /* other = origin / context id, 0 for a resource row */
+    uint32_t entered, reserved; /* entered: the node exists (always 1 for a pair row) */
+    sga_node_view view;
+} sga_node_row;
+
+/* sga_query_node's view of many nodes of one table at `now`, in one launch (one wave a node) and one wait.
+ * resources == NULL: every node of the table -- SGA_NODES_RESOURCE: the resources ClusterBuilderSlot.entry has
+ * run for, without SGA_ENTRY_NODE; a pair table: every pair with a node.  SGA_NODES_RESOURCE with a list: exactly
+ * those resources, entered or not (`entered` says which; SGA_ENTRY_NODE is allowed); a pair table with a list: the
+ * pairs of those resources.  Ids must be distinct and in range (SGA_EINVAL, checked before any launch).  Rows come
+ * back sorted by (resource, other).  More rows than cap: SGA_ERANGE, *n_out = the number needed, the first cap
+ * rows in `out` unsorted.  A pair table that was never registered: SGA_OK, 0 rows.  Every candidate node receives
+ * the window rotations of sga_query_node at `now` -- also one SGA_NODES_NOT_ZERO then drops, where the reference's
+ * totalRequest() rotates the minute window only; rotations at one `now` are idempotent. */
+int sga_query_nodes(sga_engine *e, int table, const uint32_t *resources, size_t n, int64_t now, uint32_t flags,
+                    sga_node_row *out, size_t cap, size_t *n_out);
+/* Every node of the table into DEVICE memory on `hip_stream` (NULL = engine stream), no host wait: min(count,
+ * cap) rows in no particular order, the full count in *d_count (uint32, device). */
+int sga_query_nodes_device(sga_engine *e, int table, int64_t now, uint32_t flags, sga_node_row *d_out, size_t cap,
+                           uint32_t *d_count, void *hip_stream);
+
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {
     double highest_system_load;

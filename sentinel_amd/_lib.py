@@ -104,6 +104,17 @@ class SgaNodeView(C.Structure):
                 ("previous_block_qps", C.c_double)]
 
 
+class SgaNodeRow(C.Structure):
+    _fields_ = [("resource", C.c_uint32), ("other", C.c_uint32), ("entered", C.c_uint32), ("reserved", C.c_uint32),
+                ("view", SgaNodeView)]
+
+
+# sga_query_nodes: the node table, and the flag of clusterNode?type=notZero
+SGA_NODES_RESOURCE, SGA_NODES_ORIGIN, SGA_NODES_CONTEXT = 0, 1, 2
+SGA_NODES_NOT_ZERO = 1
+SGA_EINVAL, SGA_ERANGE = -22, -34
+
+
 class SgaWireBatch(C.Structure):  # include/sga_wire.h
     _fields_ = [("cap", C.c_size_t), ("vcap", C.c_size_t), ("n", C.c_size_t), ("nv", C.c_size_t),
                 ("xid", C.c_void_p), ("type", C.c_void_p), ("kind", C.c_void_p), ("flow_id", C.c_void_p),
@@ -189,6 +200,10 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]),
     "sga_query_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
+    "sga_query_nodes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int64, C.c_uint32, C.c_void_p,
+                                  C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sga_query_nodes_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]),
     "sga_flow_set_origins": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_load_flow_rules_origin": (C.c_int, [C.c_void_p, C.POINTER(SgaFlowRule), C.c_void_p, C.c_size_t]),
     "sga_submit_events_origin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -75,6 +75,7 @@ class Engine:
         if rc < 0:
             raise _lib.EngineError(f"sga_create failed rc={rc}")
         self._h = h
+        self.device = device
         self.max_batch = max_batch
         self.set_hot_rules(hot_rules, hot_min_requests)
         self.set_small_batch(small_batch)

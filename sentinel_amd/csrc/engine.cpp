@@ -2557,6 +2557,29 @@ int sga_query_node(sga_engine *e, uint32_t resource, int64_t now, sga_node_view 
     });
 }
 
+int sga_query_nodes(sga_engine *e, int table, const uint32_t *resources, size_t n, int64_t now, uint32_t flags,
+                    sga_node_row *out, size_t cap, size_t *n_out) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.query_nodes(table, resources, n, now, flags, out, cap, n_out);
+    });
+}
+
+int sga_query_nodes_device(sga_engine *e, int table, int64_t now, uint32_t flags, sga_node_row *d_out, size_t cap,
+                           uint32_t *d_count, void *hip_stream) {
+    if (table < SGA_NODES_RESOURCE || table > SGA_NODES_CONTEXT || now < 0 || !d_count || (cap && !d_out) ||
+        (flags & ~SGA_NODES_NOT_ZERO))
+        return SGA_EINVAL;
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        hipStream_t s = g.enter_stream(hip_stream);  // the window rotations write node state
+        g.flow.launch_views(table, nullptr, 0, now, flags, d_out, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu),
+                            d_count, s);
+        g.leave_stream(s);
+        return SGA_OK;
+    });
+}
+
 int sga_flow_set_origins(sga_engine *e, uint32_t n_origins, uint32_t max_origin_nodes) {
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));

@@ -6065,43 +6065,213 @@ __global__ __launch_bounds__(kT) void k_lresults(FlowState st, FlowScratch sc, c
     }
 }
 
+// What a node view is formed from: the second window's sums over its live buckets (sec[MB_*]; sec[MB_MINRT] =
+// the least minRt of those buckets and statistic_max_rt), their largest SUCCESS, the minute window's sums, and the
+// words read as they are.  k_node_view fills it by one lane, k_node_views by a wave.
+struct NodeSums {
+    int64_t sec[kMB];
+    int64_t sec_max_succ;
+    int64_t min_pass, min_block, min_succ, min_exc;
+    int64_t threads, waiting;
+    double prev_pass, prev_block;  // minute.previousWindowPass() / previousWindowBlock()
+};
+
+// The StatisticNode getters over those integers: the one place a view's doubles are formed
+__device__ __forceinline__ sga_node_view node_view_form(const NodeSums &s) {
+    sga_node_view v;
+    v.pass_qps = (double)s.sec[MB_PASS] / 1.0;
+    v.block_qps = (double)s.sec[MB_BLOCK] / 1.0;
+    v.success_qps = (double)s.sec[MB_SUCC] / 1.0;
+    v.exception_qps = (double)s.sec[MB_EXC] / 1.0;
+    v.occupied_pass_qps = (double)s.sec[MB_OPASS] / 1.0;
+    v.avg_rt = s.sec[MB_SUCC] == 0 ? 0.0 : (double)s.sec[MB_RT] * 1.0 / (double)s.sec[MB_SUCC];
+    v.min_rt = (double)(s.sec[MB_MINRT] < 1 ? 1 : s.sec[MB_MINRT]);
+    v.previous_pass_qps = s.prev_pass;
+    v.total_pass = s.min_pass;
+    v.total_block = s.min_block;
+    v.total_success = s.min_succ;
+    v.total_exception = s.min_exc;
+    v.cur_thread_num = s.threads;
+    v.waiting = s.waiting;
+    // maxSuccessQps: ArrayMetric.maxSuccess() (currentWindow, max over values(), at least 1) x 2 / 1.0
+    v.max_success_qps = (double)(s.sec_max_succ < 1 ? 1 : s.sec_max_succ) * 2.0 / 1.0;
+    v.previous_block_qps = s.prev_block;
+    return v;
+}
+
 __global__ void k_node_view(FlowState st, int64_t max_rt, uint32_t r, int64_t now, double *dv, int64_t *iv) {
     if (threadIdx.x || blockIdx.x) return;
     const Ctx c{st, max_rt};
     int64_t *node = st.node + (size_t)r * kNodeWords;
+    NodeSums s;
     // StatisticNode getters (each rotates the current window first)
-    dv[0] = node_pass_qps(c, node, now);
     sec_current(node, now, max_rt);
-    dv[1] = (double)sec_sum(node, now, MB_BLOCK) / 1.0;
-    dv[2] = (double)sec_sum(node, now, MB_SUCC) / 1.0;
-    dv[3] = (double)sec_sum(node, now, MB_EXC) / 1.0;
-    dv[4] = (double)sec_sum(node, now, MB_OPASS) / 1.0;
-    const int64_t succ = sec_sum(node, now, MB_SUCC);
-    dv[5] = succ == 0 ? 0.0 : (double)sec_sum(node, now, MB_RT) * 1.0 / (double)succ;
-    int64_t mr = max_rt;
+    for (int f = MB_PASS; f < MB_MINRT; ++f) s.sec[f] = sec_sum(node, now, f);
+    s.sec[MB_MINRT] = max_rt;
+    s.sec_max_succ = 0;
     for (int j = 0; j < 2; ++j) {
         const int64_t *b = node + kNodeSec + kMB * j;
-        if (b[0] != kAbsent && !(now - b[0] > kSecInterval) && b[MB_MINRT] < mr) mr = b[MB_MINRT];
+        if (b[0] == kAbsent || now - b[0] > kSecInterval) continue;
+        if (b[MB_MINRT] < s.sec[MB_MINRT]) s.sec[MB_MINRT] = b[MB_MINRT];
+        if (b[MB_SUCC] > s.sec_max_succ) s.sec_max_succ = b[MB_SUCC];
     }
-    dv[6] = (double)(mr < 1 ? 1 : mr);
-    dv[7] = node_prev_pass_qps(c, node, now);
-    {  // maxSuccessQps: ArrayMetric.maxSuccess() (currentWindow, max over values(), at least 1) x 2 / 1.0
-        sec_current(node, now, max_rt);
-        int64_t ms = 0;
-        for (int j = 0; j < 2; ++j) {
-            const int64_t *b = node + kNodeSec + kMB * j;
-            if (b[0] != kAbsent && !(now - b[0] > kSecInterval) && b[MB_SUCC] > ms) ms = b[MB_SUCC];
-        }
-        dv[8] = (double)(ms < 1 ? 1 : ms) * 2.0 / 1.0;
-    }
-    dv[9] = node_prev_qps(c, node, now, MB_BLOCK);
+    s.prev_pass = node_prev_pass_qps(c, node, now);
+    s.prev_block = node_prev_qps(c, node, now, MB_BLOCK);
     min_current(node, now, max_rt);
-    iv[0] = min_sum(node, now, MB_PASS);
-    iv[1] = min_sum(node, now, MB_BLOCK);
-    iv[2] = min_sum(node, now, MB_SUCC);
-    iv[3] = min_sum(node, now, MB_EXC);
-    iv[4] = node[kNodeThreads];
-    iv[5] = node_waiting(node, now);
+    s.min_pass = min_sum(node, now, MB_PASS);
+    s.min_block = min_sum(node, now, MB_BLOCK);
+    s.min_succ = min_sum(node, now, MB_SUCC);
+    s.min_exc = min_sum(node, now, MB_EXC);
+    s.threads = node[kNodeThreads];
+    s.waiting = node_waiting(node, now);
+    const sga_node_view v = node_view_form(s);
+    dv[0] = v.pass_qps;
+    dv[1] = v.block_qps;
+    dv[2] = v.success_qps;
+    dv[3] = v.exception_qps;
+    dv[4] = v.occupied_pass_qps;
+    dv[5] = v.avg_rt;
+    dv[6] = v.min_rt;
+    dv[7] = v.previous_pass_qps;
+    dv[8] = v.max_success_qps;
+    dv[9] = v.previous_block_qps;
+    iv[0] = v.total_pass;
+    iv[1] = v.total_block;
+    iv[2] = v.total_success;
+    iv[3] = v.total_exception;
+    iv[4] = v.cur_thread_num;
+    iv[5] = v.waiting;
+}
+
+// Node views in bulk (sga_query_nodes): one wave per candidate node of one node table, kViewsWaves waves a block.
+// A candidate is entry w of `list` (a record index of the table; resource table only), record w of the resource
+// table ("all": entered ones, ENTRY_NODE = record nres left out), or slot w of a pair table (a born pair,
+// optionally of one of the sorted resources in `filt`).
+// Lane 0 applies k_node_view's rotations at `now` (second window with its borrow transfer, minute window, borrow
+// window), the block's barrier makes them visible, then lanes 0-59 read one minute bucket each, lanes 60-61 the
+// two second buckets, lane 62 the borrow pairs, curThreadNum and the entered word.  Each lane tests its own
+// bucket for deprecation; the integer sums, minRt's min and SUCCESS's max go through wave shuffles (integers: any
+// order is exact) and node_view_form makes the doubles.  Lane 0 takes the row's place from one counter.
+constexpr int kViewsWaves = 4;
+struct NodeViewsArgs {
+    int64_t *node;         // the table's records
+    uint32_t ncand;        // list entries, resource records or table slots
+    const uint32_t *list;  // resource table: explicit record indices (null: all)
+    uint32_t nres;         // resource table: record nres is ENTRY_NODE
+    PairState pair;        // pair table (node null: the resource table)
+    const uint32_t *filt;  // pair table: sorted resources to keep (null: all)
+    uint32_t nfilt;
+    uint32_t flags;        // SGA_NODES_*
+};
+
+__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a, int64_t max_rt, int64_t now,
+                                                                 sga_node_row *out, uint32_t cap, uint32_t *count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = blockIdx.x * kViewsWaves + (threadIdx.x >> 6);  // wave-uniform
+    // which node, if any (the same in every lane of the wave)
+    bool live = w < a.ncand;
+    uint32_t rec = 0, resource = 0, other = 0;
+    if (live && a.pair.node) {
+        const unsigned long long k = a.pair.key[w];
+        live = k != 0 && !(k & kPairDead) && a.pair.born[w] != kPairUnborn;
+        if (live) {
+            resource = (uint32_t)(k >> 32) - 1u;
+            other = (uint32_t)k;
+            rec = a.pair.idx[w];
+            if (a.filt) {
+                uint32_t lo = 0, hi = a.nfilt;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) / 2;
+                    if (a.filt[mid] < resource) lo = mid + 1;
+                    else hi = mid;
+                }
+                live = lo < a.nfilt && a.filt[lo] == resource;
+            }
+            live = live && rec < a.pair.max_nodes;
+        }
+    } else if (live) {
+        rec = a.list ? a.list[w] : w;
+        resource = rec == a.nres ? SGA_ENTRY_NODE : rec;
+        live = rec <= a.nres;
+    }
+    int64_t *node = a.node + (size_t)rec * kNodeWords;
+    if (live && !a.pair.node && !a.list) live = node[kNodeEntered] != 0;
+    if (live && lane == 0) {
+        bool det;
+        sec_current(node, now, max_rt);
+        min_current(node, now, max_rt);
+        bor_current(node, now, &det);
+    }
+    __syncthreads();  // every wave of the block arrives: the rotations above are visible to the wave's other lanes
+    if (!live) return;
+
+    int64_t b[kMB];
+    b[0] = kAbsent;
+#pragma unroll
+    for (int f = 1; f < kMB; ++f) b[f] = 0;
+    NodeSums s;
+    int64_t entered = 0;
+    s.threads = s.waiting = 0;
+    s.prev_pass = s.prev_block = 0.0;
+    if (lane < 62) {
+        const int64_t *p = node + (lane < 60 ? kNodeMin + kMB * (int)lane : kNodeSec + kMB * (int)(lane - 60));
+#pragma unroll
+        for (int f = 0; f < kMB; ++f) b[f] = p[f];
+        if (b[0] == kAbsent || now - b[0] > (lane < 60 ? kMinInterval : kSecInterval)) {
+#pragma unroll
+            for (int f = 1; f < MB_MINRT; ++f) b[f] = 0;
+            b[MB_MINRT] = max_rt;
+        }
+    } else if (lane == 62) {
+        const Ctx c{FlowState{}, max_rt};
+        s.threads = node[kNodeThreads];
+        entered = node[kNodeEntered];
+        s.waiting = node_waiting(node, now);
+        s.prev_pass = node_prev_pass_qps(c, node, now);
+        s.prev_block = node_prev_qps(c, node, now, MB_BLOCK);
+    }
+    // minute window: lanes 0-59 hold a bucket each, the others zeros
+    const bool mn = lane < 60;
+    s.min_pass = wave_sum64(mn ? b[MB_PASS] : 0);
+    s.min_block = wave_sum64(mn ? b[MB_BLOCK] : 0);
+    s.min_succ = wave_sum64(mn ? b[MB_SUCC] : 0);
+    s.min_exc = wave_sum64(mn ? b[MB_EXC] : 0);
+    // second window: two lanes, read across the wave
+    int64_t b0[kMB], b1[kMB];
+#pragma unroll
+    for (int f = 1; f < kMB; ++f) {
+        b0[f] = __shfl(b[f], 60, 64);
+        b1[f] = __shfl(b[f], 61, 64);
+    }
+#pragma unroll
+    for (int f = 1; f < MB_MINRT; ++f) s.sec[f] = b0[f] + b1[f];
+    s.sec[MB_START] = 0;
+    s.sec[MB_MINRT] = b0[MB_MINRT] < b1[MB_MINRT] ? b0[MB_MINRT] : b1[MB_MINRT];
+    if (max_rt < s.sec[MB_MINRT]) s.sec[MB_MINRT] = max_rt;
+    s.sec_max_succ = b0[MB_SUCC] > b1[MB_SUCC] ? b0[MB_SUCC] : b1[MB_SUCC];
+    if (s.sec_max_succ < 0) s.sec_max_succ = 0;
+    s.threads = __shfl(s.threads, 62, 64);
+    s.waiting = __shfl(s.waiting, 62, 64);
+    s.prev_pass = __shfl(s.prev_pass, 62, 64);
+    s.prev_block = __shfl(s.prev_block, 62, 64);
+    entered = __shfl(entered, 62, 64);
+    if (lane) return;
+    if ((a.flags & SGA_NODES_NOT_ZERO) && !(s.min_pass + s.min_block > 0)) return;
+    const uint32_t k = atomicAdd(count, 1u);
+    if (k >= cap) return;
+    sga_node_row row;
+    row.resource = resource;
+    row.other = other;
+    row.entered = a.pair.node ? 1u : (uint32_t)(entered != 0);  // a pair's record exists from its first entry on
+    row.reserved = 0;
+    row.view = node_view_form(s);
+    out[k] = row;
 }
 
 __global__ void k_init_nodes(int64_t *node, uint32_t n, int64_t max_rt) {
@@ -7779,6 +7949,81 @@ int FlowEngine::query_at(int64_t *nodes, uint32_t r, int64_t now, sga_node_view 
     out->waiting = iv[5];
     out->max_success_qps = dv[8];
     out->previous_block_qps = dv[9];
+    return 0;
+}
+
+size_t FlowEngine::launch_views(int table, const uint32_t *d_list, uint32_t n, int64_t now, uint32_t flags,
+                                sga_node_row *d_out, uint32_t cap, uint32_t *d_count, hipStream_t s) {
+    SGA_HIP_CHECK(hipMemsetAsync(d_count, 0, 4, s));
+    NodeViewsArgs a{};
+    a.flags = flags;
+    a.nres = nres;
+    size_t most;
+    if (table == SGA_NODES_RESOURCE) {
+        a.node = d_node.p;
+        a.list = d_list;
+        a.ncand = d_list ? n : nres;
+        most = a.ncand;
+    } else {
+        const PairTable &t = ptab[table == SGA_NODES_ORIGIN ? kPairOrigin : kPairContext];
+        if (!t.n_ids) return 0;
+        a.pair = pstate().t[table == SGA_NODES_ORIGIN ? kPairOrigin : kPairContext];
+        a.node = a.pair.node;
+        a.filt = d_list;
+        a.nfilt = n;
+        a.ncand = t.slots;
+        most = d_list ? std::min<size_t>(t.max_nodes, (size_t)n * t.n_ids) : t.max_nodes;
+    }
+    if (!a.ncand) return 0;
+    hipLaunchKernelGGL(k_node_views, dim3((a.ncand + kViewsWaves - 1) / kViewsWaves), dim3(64 * kViewsWaves), 0, s, a,
+                       (int64_t)cfg.statistic_max_rt, now, d_out, cap, d_count);
+    SGA_HIP_CHECK(hipGetLastError());
+    return most;
+}
+
+int FlowEngine::query_nodes(int table, const uint32_t *resources, size_t n, int64_t now, uint32_t flags,
+                            sga_node_row *out, size_t cap, size_t *n_out) {
+    if (table < SGA_NODES_RESOURCE || table > SGA_NODES_CONTEXT || now < 0 || !n_out || (cap && !out) ||
+        (flags & ~SGA_NODES_NOT_ZERO))
+        return SGA_EINVAL;
+    *n_out = 0;
+    // the list, as record indices (resource table) or the filter (pair tables): distinct and in range, so that no
+    // two waves rotate one node
+    std::vector<uint32_t> ids;
+    if (resources) {
+        ids.assign(resources, resources + n);
+        for (uint32_t &r : ids) {
+            if (r == SGA_ENTRY_NODE && table == SGA_NODES_RESOURCE && nres) r = nres;
+            else if (r >= nres) return SGA_EINVAL;
+        }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return SGA_EINVAL;
+        if (ids.empty()) return 0;
+    }
+    if (!nres) return 0;
+    size_t most = nres;
+    if (resources) most = n;
+    if (table != SGA_NODES_RESOURCE) {
+        const PairTable &t = ptab[table == SGA_NODES_ORIGIN ? kPairOrigin : kPairContext];
+        if (!t.n_ids) return 0;
+        most = resources ? std::min<size_t>(t.max_nodes, n * (size_t)t.n_ids) : t.max_nodes;
+    }
+    const uint32_t dcap = (uint32_t)std::min<size_t>(cap, most);
+    if (d_rows.n < std::max<size_t>(dcap, 1)) d_rows.alloc(std::max<size_t>(dcap, 1));
+    if (d_vlist.n < ids.size() + 1) d_vlist.alloc(ids.size() + 1);
+    if (!ids.empty())
+        SGA_HIP_CHECK(hipMemcpyAsync(d_vlist.p + 1, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, stream));
+    launch_views(table, ids.empty() ? nullptr : d_vlist.p + 1, (uint32_t)ids.size(), now, flags, d_rows.p, dcap,
+                 d_vlist.p, stream);
+    uint32_t cnt = 0;
+    SGA_HIP_CHECK(hipMemcpyAsync(&cnt, d_vlist.p, 4, hipMemcpyDeviceToHost, stream));
+    if (dcap) SGA_HIP_CHECK(hipMemcpyAsync(out, d_rows.p, (size_t)dcap * sizeof(sga_node_row), hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    *n_out = cnt;
+    if (cnt > cap) return SGA_ERANGE;
+    std::sort(out, out + cnt, [](const sga_node_row &x, const sga_node_row &y) {
+        return x.resource != y.resource ? x.resource < y.resource : x.other < y.other;
+    });
     return 0;
 }
 

@@ -463,6 +463,14 @@ struct FlowEngine {
     DevBuf<uint32_t> d_gate;  // [0] gate word of the running chunk, [1] sticky error bits
     int query(uint32_t resource, int64_t now, sga_node_view *out);
     int query_at(int64_t *nodes, uint32_t index, int64_t now, sga_node_view *out);
+    // sga_query_nodes / sga_query_nodes_device: k_node_views over one table.  launch_views returns the number of
+    // rows the launch can produce at most (0: nothing launched, *d_count zeroed)
+    DevBuf<sga_node_row> d_rows;
+    DevBuf<uint32_t> d_vlist;  // [0] the row counter, then the explicit list or the pair filter
+    size_t launch_views(int table, const uint32_t *d_list, uint32_t n, int64_t now, uint32_t flags,
+                        sga_node_row *d_out, uint32_t cap, uint32_t *d_count, hipStream_t s);
+    int query_nodes(int table, const uint32_t *resources, size_t n, int64_t now, uint32_t flags, sga_node_row *out,
+                    size_t cap, size_t *n_out);
     int cb_state(uint32_t resource, uint32_t k);
     int metrics(int64_t now, sga_metric_node *out, size_t cap, size_t *n);
     int load_system_rules(const sga_system_rule *r, size_t n);

@@ -15,6 +15,10 @@ Same names and argument meaning as the Java API the engine replaces:
   ContextUtil.enter(name, ...)    the `context` of entry / submit; NodeSelectorSlot's DefaultNode per (resource,
                                   context), CORE/slots/nodeselector/NodeSelectorSlot.java:158-177
                                   -> LocalSentinel.default_node / default_nodes
+  ClusterBuilderSlot.getClusterNodeMap, getOriginCountMap read whole (the command center's clusterNode, cnode,
+                                  origin) -> LocalSentinel.nodes / origin_node_views / default_node_views /
+                                  nodes_device (sga_query_nodes: one launch for any number of nodes)
+  FlowRuleManager.getRules and its siblings -> the managers' get_rules
 BlockException subclasses as in CORE/slots/block/BlockException.java and its subclasses.
 
 Every decision is computed by the HIP engine (libsentinel_amd.so).  The mocked
@@ -142,6 +146,11 @@ class NodeView:
     previous_block_qps: float
 
 
+# one sga_node_row (sga_query_nodes): the row's ids, then the NodeView fields under their names
+NODE_ROW_DTYPE = np.dtype([("resource", "<u4"), ("other", "<u4"), ("entered", "<u4"), ("reserved", "<u4")] +
+                          [(f, "<f8" if t is C.c_double else "<i8") for f, t in SgaNodeView._fields_])
+
+
 @dataclass
 class MetricNode:
     """CORE/node/metric/MetricNode.java:28-51 (one resource, one second)."""
@@ -227,6 +236,8 @@ class LocalSentinel:
             raise ValueError("duplicate context names")
         if any(not c for c in self.contexts):
             raise ValueError("context name '' is reserved")
+        # records of the two pair tables (0 = the engine's default of 16,384): the most rows a bulk view can give
+        self._max_pair_nodes = (max_origin_nodes or 1 << 14, max_context_nodes or 1 << 14)
         check(_lib.load().sga_flow_set_resources(engine.handle, len(self.resources)), engine.handle, "setResources")
         if self.origins:
             check(_lib.load().sga_flow_set_origins(engine.handle, len(self.origins), max_origin_nodes),
@@ -470,6 +481,77 @@ class LocalSentinel:
               self.engine.handle, "defaultNodes")
         return [self.contexts[i - 1] for i in sorted(buf[:n.value])]
 
+    # ---- node views in bulk (sga_query_nodes: one launch, one wave a node)
+    def query_nodes(self, table: int, now: int, resources=None, flags: int = 0) -> np.ndarray:
+        """Rows of sga_query_nodes as a NODE_ROW_DTYPE array sorted by (resource, other).  resources: ids of this
+        table's resources (None: every node of the table)."""
+        ids = None if resources is None else np.ascontiguousarray(resources, dtype=np.uint32)
+        if table == _lib.SGA_NODES_RESOURCE:
+            cap = len(self.resources) if ids is None else len(ids)
+        else:
+            reg, most = ((self.origins, self._max_pair_nodes[0]) if table == _lib.SGA_NODES_ORIGIN else
+                         (self.contexts, self._max_pair_nodes[1]))
+            cap = 0 if not reg else most if ids is None else min(most, len(ids) * len(reg))
+        n = C.c_size_t()
+        for _ in range(2):  # the first cap holds every row the table can give
+            out = np.zeros(max(1, cap), dtype=NODE_ROW_DTYPE)
+            rc = _lib.load().sga_query_nodes(self.engine.handle, table, None if ids is None else ids.ctypes.data,
+                                             0 if ids is None else len(ids), now, flags, out.ctypes.data, cap,
+                                             C.byref(n))
+            if rc != _lib.SGA_ERANGE:
+                break
+            cap = n.value
+        check(rc, self.engine.handle, "nodes")
+        return out[:n.value]
+
+    @staticmethod
+    def _view_of(row) -> NodeView:
+        return NodeView(*[row[f].item() for f, _ in SgaNodeView._fields_])
+
+    def nodes(self, now: int, resources=None, not_zero: bool = False):
+        """[(name, NodeView)] in ascending resource id.  resources None: the ClusterNodes that exist
+        (ClusterBuilderSlot.getClusterNodeMap: entered resources, without ENTRY_NODE); a list of names / ids
+        (ENTRY_NODE allowed): exactly those, entered or not.  not_zero: only nodes with totalRequest() > 0."""
+        ids = None
+        if resources is not None:
+            ids = [ENTRY_NODE if r == TOTAL_IN_RESOURCE_NAME else r if isinstance(r, int) else self.ids[r]
+                   for r in resources]
+        rows = self.query_nodes(_lib.SGA_NODES_RESOURCE, now, ids, _lib.SGA_NODES_NOT_ZERO if not_zero else 0)
+        return [(TOTAL_IN_RESOURCE_NAME if int(r["resource"]) == ENTRY_NODE else self.resources[int(r["resource"])],
+                 self._view_of(r)) for r in rows]
+
+    def origin_node_views(self, resource, now: int):
+        """[(origin name, NodeView)] of the resource's origin nodes (getOriginCountMap), ascending origin id."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        rows = self.query_nodes(_lib.SGA_NODES_ORIGIN, now, [rid])
+        return [(self.origins[int(r["other"]) - 1], self._view_of(r)) for r in rows]
+
+    def default_node_views(self, resource, now: int):
+        """[(context name, NodeView)] of the resource's DefaultNodes, ascending context id."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        rows = self.query_nodes(_lib.SGA_NODES_CONTEXT, now, [rid])
+        return [(self.contexts[int(r["other"]) - 1], self._view_of(r)) for r in rows]
+
+    def nodes_device(self, now: int, table: int = 0, not_zero: bool = False, cap: Optional[int] = None, stream=None):
+        """Every node of the table into device memory (sga_query_nodes_device), asynchronous on `stream` (a torch
+        stream; None = the engine stream): (rows, count) torch tensors on the engine's GPU -- rows uint8 of shape
+        (cap, 144), one sga_node_row each (NODE_ROW_DTYPE once on the host), in no particular order; count int32
+        of shape (1,), the full number of rows, of which min(count, cap) are written (the rest of `rows` is not
+        initialised).  Work on another stream must wait for `stream`; with the engine stream, sga_sync
+        waits for it on the host."""
+        import torch
+        if cap is None:
+            cap = len(self.resources) if table == _lib.SGA_NODES_RESOURCE else self._max_pair_nodes[table - 1]
+        dev = torch.device("cuda", self.engine.device)
+        # empty, not zeros: a fill on torch's stream would race with the engine's writes on another
+        rows = torch.empty((max(1, cap), NODE_ROW_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        check(_lib.load().sga_query_nodes_device(self.engine.handle, table, now,
+                                                 _lib.SGA_NODES_NOT_ZERO if not_zero else 0, rows.data_ptr(), cap,
+                                                 count.data_ptr(), stream.cuda_stream if stream is not None else None),
+              self.engine.handle, "nodesDevice")
+        return rows, count
+
     def metrics(self, now: int, cap: int = 1 << 16) -> List[MetricNode]:
         """MetricTimerListener.run (CORE/node/metric/MetricTimerListener.java:44-65): StatisticNode.metrics()
         of every resource at `now`, ordered by timestamp then resource (the TreeMap the reference writes)."""
@@ -520,11 +602,17 @@ class FlowRuleManager:
     def __init__(self, sentinel: LocalSentinel):
         self.s = sentinel
 
+    def get_rules(self) -> list:
+        """The list last loaded (the reference's getRules()); a rule naming a resource this sentinel does not
+        have stays in it and applies to nothing, like a rule of a resource nobody enters."""
+        return list(getattr(self, "_rules", []))
+
     def load_rules(self, rules: List[FlowRule]) -> int:
         """FlowRuleManager.loadRules.  Cluster-mode rules ask the token service when checked
         (FlowRuleChecker.passClusterCheck): with ClusterStateManager set to server the engine's own
         cluster rules (ClusterFlowRuleManager on the same Engine) decide their flowId, otherwise
         they fall back (fallbackToLocalWhenFail: the local rater, else pass)."""
+        self._rules = list(rules)
         rules = [r for r in rules if r.resource in self.s.ids]
         arr = (SgaFlowRule * max(1, len(rules)))()
         # a sentinel with registered origins names each rule's limitApp by id (sga_load_flow_rules_origin: the rule
@@ -588,7 +676,13 @@ class ParamFlowRuleManager:
         self.s = sentinel
         self._keep = []
 
+    def get_rules(self) -> list:
+        """The list last loaded (the reference's getRules()); a rule naming a resource this sentinel does not
+        have stays in it and applies to nothing, like a rule of a resource nobody enters."""
+        return list(getattr(self, "_rules", []))
+
     def load_rules(self, rules: List[ParamFlowRule]) -> int:
+        self._rules = list(rules)
         rules = [r for r in rules if r.resource in self.s.ids]
         arr = (SgaParamRule * max(1, len(rules)))()
         keep = []
@@ -628,7 +722,13 @@ class DegradeRuleManager:
     def __init__(self, sentinel: LocalSentinel):
         self.s = sentinel
 
+    def get_rules(self) -> list:
+        """The list last loaded (the reference's getRules()); a rule naming a resource this sentinel does not
+        have stays in it and applies to nothing, like a rule of a resource nobody enters."""
+        return list(getattr(self, "_rules", []))
+
     def load_rules(self, rules: List[DegradeRule]) -> int:
+        self._rules = list(rules)
         rules = [r for r in rules if r.resource in self.s.ids]
         arr = (SgaDegradeRule * max(1, len(rules)))()
         for i, r in enumerate(rules):
@@ -660,7 +760,13 @@ class SystemRuleManager:
     def __init__(self, sentinel: LocalSentinel):
         self.s = sentinel
 
+    def get_rules(self) -> list:
+        """The list last loaded (the reference's getRules()); a rule naming a resource this sentinel does not
+        have stays in it and applies to nothing, like a rule of a resource nobody enters."""
+        return list(getattr(self, "_rules", []))
+
     def load_rules(self, rules: List[SystemRule]) -> int:
+        self._rules = list(rules)
         arr = (_lib.SgaSystemRule * max(1, len(rules)))()
         for i, r in enumerate(rules):
             arr[i].highest_system_load = r.highest_system_load
@@ -671,5 +777,8 @@ class SystemRuleManager:
         return check(_lib.load().sga_load_system_rules(self.s.engine.handle, arr, len(rules)), self.s.engine.handle,
                      "SystemRuleManager.loadRules")
 
+    avg_load, cpu_usage = -1.0, -1.0  # SystemRuleManager.getCurrentSystemAvgLoad / getCurrentCpuUsage (-1: not measured)
+
     def set_system_status(self, avg_load: float, cpu_usage: float):
+        self.avg_load, self.cpu_usage = float(avg_load), float(cpu_usage)
         check(_lib.load().sga_set_system_status(self.s.engine.handle, avg_load, cpu_usage), self.s.engine.handle)
