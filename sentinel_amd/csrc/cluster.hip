@@ -1864,6 +1864,30 @@ __device__ __forceinline__ uint32_t hot_precheck(const ClusterState &st, const B
     return bad ? (uint32_t)kFlagState : flag;
 }
 
+// Profiling only (built with -DSGA_KEY_PHASES=1, never in the product library; every result stays exact): pass 0's
+// first wave stamps the phases of its workgroup, wall_clock64 ticks summed over the workgroups --
+// [0] entry -> first record loads issued, [1] -> first chunk looked up (the prologue; the streaming loop starts),
+// [2] the streaming loop, [3] the rank pass, [4] scan + count row, [5] fix-up + hcode, [6] the rest, [7] workgroups.
+// Each hot-path batch then waits for them and prints their averages (cold_stage_and_next).
+#ifdef SGA_KEY_PHASES
+__device__ unsigned long long g_key_phase[8];
+#define KEY_MARK_BEGIN unsigned long long kt_ = wall_clock64()
+#define KEY_MARK(ph)                                         \
+    do {                                                     \
+        if (kPass == 0 && threadIdx.x == 0) {                \
+            const unsigned long long now_ = wall_clock64();  \
+            atomicAdd(&g_key_phase[ph], now_ - kt_);         \
+            kt_ = now_;                                      \
+        }                                                    \
+    } while (0)
+#else
+#define KEY_MARK_BEGIN \
+    do {               \
+    } while (0)
+#define KEY_MARK(ph) \
+    do {             \
+    } while (0)
+#endif
 struct KeyShared {
     WConst wcs[256];
     uint16_t cnt[kKeyWaves][kHot];  // per wave: hot requests so far per hot id
@@ -1886,6 +1910,7 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
     const uint8_t *__restrict__ prio = in.prio;
     const uint32_t *__restrict__ ts_off = in.ts;
     const uint32_t *__restrict__ pk = in.pk;
+    KEY_MARK_BEGIN;
     // d0 > 0: the LSD sort's first digit (d0 bits) counted per sort tile; d0 < 0: partition mode, the
     // cold elements counted per slot bin (slot >> -d0) into the segment's row of hist ([seg][kPartBins])
     WConst *wcs = sh.wcs;
@@ -1894,9 +1919,72 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
     const uint32_t dmask = (1u << d0) - 1u;
     auto &cnt = sh.cnt;
     uint32_t *s_np = sh.s_np, *s_bd = sh.s_bd;
-    const uint32_t nhot = kPass == 0 ? hot_count(sc) : 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t lt = lanemask_lt64(lane);
+    const uint32_t sub = seg * kKeyWaves + wave;
+    const uint32_t ubase = sub * kSubSeg;
+    const bool active = ubase < n;
+    const bool use_prio = kPk || prio != nullptr;
+    constexpr int nchunks = kSubRounds / kH1Chunk;  // a short last sub runs masked rounds
+    struct Buf {
+        int64_t f[kH1Chunk];
+        int32_t a[kH1Chunk];
+        uint32_t t[kH1Chunk], p[kH1Chunk], d[kH1Chunk], m[kH1Chunk];
+        HashEntry e[kH1Chunk];
+    };
+    Buf B0, B1, B2;
+    // a missing prio array reads the acquire bytes instead, masked off when processed
+    const uint8_t *pr_src = kPk ? nullptr : (use_prio ? prio : reinterpret_cast<const uint8_t *>(acquire));
+    auto load = [&](int ch, Buf &B) {
+#pragma unroll
+        for (int u = 0; u < kH1Chunk; ++u) {
+            const uint32_t i = min(ubase + (uint32_t)(ch * kH1Chunk + u) * 64 + lane, n - 1);
+            if (kPk) {  // one 12-byte record: flowId, time offset, acquireCount | flags << 16
+                const uint32_t *r = pk + 3 * (size_t)i;
+                uint32_t w0, w1, w2;
+                if (kNT) {
+                    w0 = __builtin_nontemporal_load(r);
+                    w1 = __builtin_nontemporal_load(r + 1);
+                    w2 = __builtin_nontemporal_load(r + 2);
+                } else {
+                    w0 = r[0];
+                    w1 = r[1];
+                    w2 = r[2];
+                }
+                B.f[u] = (int64_t)w0;
+                B.t[u] = w1;
+                B.a[u] = (int32_t)(w2 & 0xFFFFu);
+                B.p[u] = w2 >> 16;  // the flags: bit 0 prioritized, other bits reserved (BAD_REQUEST)
+            } else if (kNT) {  // streamed once: non-temporal, so the dense table keeps more of L2
+                B.f[u] = __builtin_nontemporal_load(&flow_id[i]);
+                B.a[u] = __builtin_nontemporal_load(&acquire[i]);
+                B.t[u] = __builtin_nontemporal_load(&ts_off[i]);
+                B.p[u] = __builtin_nontemporal_load(&pr_src[i]);
+            } else {
+                B.f[u] = flow_id[i];
+                B.a[u] = acquire[i];
+                B.t[u] = ts_off[i];
+                B.p[u] = pr_src[i];
+            }
+        }
+    };
+    // The first two chunks' records and the time of the request before the sub (time order and bucket
+    // boundaries across the sub start) are asked for before anything else: they depend on the sub's place alone,
+    // so they are in flight while the LDS is cleared and the control words are read, instead of after three
+    // dependent reads of those.  Clamped indices like every load of the pipeline; a wave past the batch's end
+    // loads the last record and ignores it.  (The four-array form, with its wider buffers, asks for its records
+    // where it always did: held over the prologue they cost it registers it does not have.)
+    if (kPk) {
+        load(0, B0);
+        load(1, B1);
+    }
+    const uint32_t pidx = min(ubase > 0 ? ubase - 1 : 0u, n - 1);
+    uint32_t ptso = kPk ? pk[3 * (size_t)pidx + 1] : ts_off[pidx];  // (request 0 has no predecessor: not looked at)
+    // (a compiler barrier: the scheduler otherwise puts the control words' dependent reads and the window
+    // table's first load, each with its wait, ahead of these independent loads)
+    asm volatile("" ::: "memory");
+    KEY_MARK(0);
+    const uint32_t nhot = kPass == 0 ? hot_count(sc) : 0u;
     if (kDense)  // r0 and 1/W of every window-length code (the dense flowId table's wcode)
         for (int k = threadIdx.x; k < 256; k += kKeyThreads) {
             const uint32_t W = st.wtab[k];
@@ -1916,9 +2004,6 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
         sh.s_bmax = 0u;
     }
     __syncthreads();
-    const uint32_t sub = seg * kKeyWaves + wave;
-    const uint32_t ubase = sub * kSubSeg;
-    const bool active = ubase < n;
     uint16_t *c = cnt[wave];
     const uint32_t Wh = nhot ? sc.hot_ctl[2] : 1u;
     const uint32_t r0h = (uint32_t)(ts_base % (int64_t)Wh);
@@ -1935,53 +2020,8 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
 #pragma unroll
     for (int r = 0; r < kSubRounds; ++r) hc[r] = kNoCode;
     if (active) {
-        uint32_t ptso = ubase > 0 ? (kPk ? pk[3 * (size_t)(ubase - 1) + 1] : ts_off[ubase - 1]) : 0u;  // time order across the sub start
         // hot bucket of the previous request (bucket boundaries)
         uint32_t pbd = (nhot && ubase > 0) ? min(bucket_delta(ptso, Wh, r0h, invh), (uint32_t)kHotBuckets - 1) : 0u;
-        const bool use_prio = kPk || prio != nullptr;
-        constexpr int nchunks = kSubRounds / kH1Chunk;  // a short last sub runs masked rounds
-        struct Buf {
-            int64_t f[kH1Chunk];
-            int32_t a[kH1Chunk];
-            uint32_t t[kH1Chunk], p[kH1Chunk], d[kH1Chunk], m[kH1Chunk];
-            HashEntry e[kH1Chunk];
-        };
-        Buf B0, B1, B2;
-        // a missing prio array reads the acquire bytes instead, masked off when processed
-        const uint8_t *pr_src = kPk ? nullptr : (use_prio ? prio : reinterpret_cast<const uint8_t *>(acquire));
-        auto load = [&](int ch, Buf &B) {
-#pragma unroll
-            for (int u = 0; u < kH1Chunk; ++u) {
-                const uint32_t i = min(ubase + (uint32_t)(ch * kH1Chunk + u) * 64 + lane, n - 1);
-                if (kPk) {  // one 12-byte record: flowId, time offset, acquireCount | flags << 16
-                    const uint32_t *r = pk + 3 * (size_t)i;
-                    uint32_t w0, w1, w2;
-                    if (kNT) {
-                        w0 = __builtin_nontemporal_load(r);
-                        w1 = __builtin_nontemporal_load(r + 1);
-                        w2 = __builtin_nontemporal_load(r + 2);
-                    } else {
-                        w0 = r[0];
-                        w1 = r[1];
-                        w2 = r[2];
-                    }
-                    B.f[u] = (int64_t)w0;
-                    B.t[u] = w1;
-                    B.a[u] = (int32_t)(w2 & 0xFFFFu);
-                    B.p[u] = w2 >> 16;  // the flags: bit 0 prioritized, other bits reserved (BAD_REQUEST)
-                } else if (kNT) {  // streamed once: non-temporal, so the dense table keeps more of L2
-                    B.f[u] = __builtin_nontemporal_load(&flow_id[i]);
-                    B.a[u] = __builtin_nontemporal_load(&acquire[i]);
-                    B.t[u] = __builtin_nontemporal_load(&ts_off[i]);
-                    B.p[u] = __builtin_nontemporal_load(&pr_src[i]);
-                } else {
-                    B.f[u] = flow_id[i];
-                    B.a[u] = acquire[i];
-                    B.t[u] = ts_off[i];
-                    B.p[u] = pr_src[i];
-                }
-            }
-        };
         auto lookup = [&](Buf &B) {
 #pragma unroll
             for (int u = 0; u < kH1Chunk; ++u) {
@@ -2130,9 +2170,10 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
                 nc += (uint32_t)__popcll(em);
             }
         };
-        load(0, B0);
+        if (!kPk) load(0, B0);
         lookup(B0);
-        load(1, B1);
+        if (!kPk) load(1, B1);
+        KEY_MARK(1);
 #pragma unroll
         for (int ch = 0; ch < nchunks; ch += 3) {
             lookup(B1);
@@ -2147,6 +2188,7 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
             load(ch + 4, B1);
             process(B2, ch + 2);
         }
+        KEY_MARK(2);
         if (nhot) {
             // rank pass over the sub's keys (just written: L2; all 16 loads in flight together, the
             // pipeline's registers are free), one round at a time
@@ -2163,6 +2205,7 @@ __device__ __forceinline__ void hot_key(KeyShared &sh, const ClusterState &st, c
             }
         }
     }
+    KEY_MARK(3);
     if (wflags) atomicOr(&sc.counters[CTL_FLAGS], wflags);
     if (nhot) {
 bdmax = wave_max_u32(bdmax);
@@ -2191,6 +2234,7 @@ bdmax = wave_max_u32(bdmax);
             sc.seg_stat[kSegStat * seg] = a;
         }
         __syncthreads();
+        KEY_MARK(4);
         if (active) {
             // codes: in-wave ranks -> in-segment ranks; prioritized hot requests go to the segment's
             // prioritized buffer, compacted over the segment in arrival order (the waves' counts s_np give each
@@ -2218,6 +2262,7 @@ bdmax = wave_max_u32(bdmax);
         // Per hot bucket whose first request P lies inside this segment (not at its start): the segment's hot
         // requests of each hot id before P (k_hot_flows adds them to the segment's base rank).  On the hot path
         // the times are sorted, so "before P" is "of an earlier bucket".  Rare (a few segments per batch).
+        KEY_MARK(5);
         __syncthreads();  // the fix-up's reads of the wave prefixes are done: cnt is free
         const uint32_t b0 = sh.s_bmin, b1 = sh.s_bmax;
         uint32_t *pc = reinterpret_cast<uint32_t *>(&cnt[0][0]);
@@ -2280,6 +2325,10 @@ bdmax = wave_max_u32(bdmax);
             if (tile < ntiles) hist[(size_t)d * ntiles + tile] = sh.hist0[t][d];
         }
     }
+    KEY_MARK(6);
+#ifdef SGA_KEY_PHASES
+    if (kPass == 0 && threadIdx.x == 0) atomicAdd(&g_key_phase[7], 1ull);
+#endif
 }
 
 // ---- cold partition (hot path; SURVEY hard part 4): the key kernels count each segment's cold elements
@@ -4202,6 +4251,19 @@ static void cold_stage_and_next(const ClusterState &st, BatchScratch &sc, const 
             fprintf(stderr, "fz phases (wall_clock64 ticks per workgroup, %llu wgs): order %.0f runs %.0f flows %.0f results %.0f\n",
                     ph[7], (double)ph[3] / ph[7], (double)ph[0] / ph[7], (double)ph[1] / ph[7], (double)ph[2] / ph[7]);
     }
+#ifdef SGA_KEY_PHASES
+    {  // profiling only: pass 0's phase ticks per workgroup (100 ticks per us)
+        unsigned long long ph[8];
+        SGA_HIP_CHECK(hipMemcpyFromSymbolAsync(ph, HIP_SYMBOL(g_key_phase), sizeof(ph), 0, hipMemcpyDeviceToHost, s));
+        SGA_HIP_CHECK(hipStreamSynchronize(s));
+        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        SGA_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_key_phase), z, sizeof(z), 0, hipMemcpyHostToDevice, s));
+        if (ph[7])
+            fprintf(stderr, "key phases (us per workgroup, %llu wgs): to-first-load %.2f to-loop %.2f loop %.2f rank %.2f scan %.2f fixup %.2f rest %.2f\n",
+                    ph[7], ph[0] / 100.0 / ph[7], ph[1] / 100.0 / ph[7], ph[2] / 100.0 / ph[7], ph[3] / 100.0 / ph[7],
+                    ph[4] / 100.0 / ph[7], ph[5] / 100.0 / ph[7], ph[6] / 100.0 / ph[7]);
+    }
+#endif
     SGA_HIP_CHECK(hipStreamWaitEvent(s, sc.ev_mid, 0));
     const uint32_t sb = 64;  // few workgroups: their bins meet in global atomics
     hipLaunchKernelGGL(k_hot_next_a, dim3(sb), dim3(kThreads), 0, s, st, sc, hot_min);
