@@ -399,8 +399,10 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
  * default sentinel_default_context, whose DefaultNodes nobody reads: such an event creates and counts no
  * context node (a deployment that wants a rule on the default context registers that name like any other).
  * An entry under NullContext (past 2,000 context names, ContextUtil.trueEnter) skips the slot chain
- * altogether: such entries are simply never submitted.  EntranceNodes and the invocation tree are not
- * modelled: the engine does not see entry nesting.
+ * altogether: such entries are simply never submitted.  The invocation tree is opt-in per call: events
+ * submitted with a parent array (sga_submit_events_tree*) record each DefaultNode's parent at its creation, and
+ * sga_query_tree answers the DefaultNodes with their edges; EntranceNodes and Constants.ROOT hold no counters of
+ * their own (sums over their children, formed by the host).
  * ------------------------------------------------------------------------- */
 
 /* Coalescing queue of single local events (SphU.entry / Entry.exit from many application threads, one
@@ -740,6 +742,49 @@ int sga_query_nodes(sga_engine *e, int table, const uint32_t *resources, size_t 
  * cap) rows in no particular order, the full count in *d_count (uint32, device). */
 int sga_query_nodes_device(sga_engine *e, int table, int64_t now, uint32_t flags, sga_node_row *d_out, size_t cap,
                            uint32_t *d_count, void *hip_stream);
+
+/* ---- invocation tree (new entry points only): what the command center's tree and jsonTree commands read ---- */
+/* "no enclosing DefaultNode": the pair hangs under its context's EntranceNode */
+#define SGA_PARENT_ENTRANCE 0xFFFFFFFFu
+
+/* The _ctx entries with the enclosing entry per event (parent[n], after context; NULL = every event is
+ * outermost): parent[i] is the resource id of the entry that encloses event i in its context, or
+ * SGA_PARENT_ENTRANCE.  It is the edge NodeSelectorSlot.entry takes when it creates a DefaultNode --
+ * ((DefaultNode) context.getLastNode()).addChild(node), NodeSelectorSlot.java:158-177, once, at creation -- so it
+ * is read only for a kind 0 / 2 / 3 event with context != 0 on a known resource, and kept only from the pair's
+ * first such event in arrival order; later entries of the pair under another parent add no edge, exits ignore it.
+ * On such an event an id >= n_resources that is not SGA_PARENT_ENTRANCE refuses the whole call or chunk as an
+ * origin id above n_origins does (SGA_EINVAL, nothing applied, claims taken back; device entry: -1 for every event
+ * and sga_events_device_status).  Decisions, waits and every node's counts equal those of the same events through
+ * sga_submit_events_ctx*; a DefaultNode born through any entry point without a parent array hangs under its
+ * EntranceNode. */
+int sga_submit_events_tree(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
+                           const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
+                           const uint32_t *origin, const uint32_t *context, const uint32_t *parent, size_t n,
+                           const uint64_t *param_values, size_t n_values, int8_t *decision, int32_t *wait_ms);
+int sga_submit_events_tree_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base,
+                                  const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags,
+                                  const int64_t *d_rt, const uint64_t *d_param, const uint32_t *d_origin,
+                                  const uint32_t *d_context, const uint32_t *d_parent, size_t n,
+                                  const uint64_t *d_param_values, size_t n_values, int8_t *d_decision,
+                                  int32_t *d_wait_ms, void *hip_stream);
+
+typedef struct sga_tree_row {
+    uint32_t resource, context;
+    uint32_t parent;   /* the resolved edge: a resource id of the same context, or SGA_PARENT_ENTRANCE */
+    uint32_t reserved;
+    sga_node_view view;
+} sga_tree_row;
+
+/* One row per DefaultNode, sorted by (context, resource), in one launch (one wave a node) and one wait.  view is
+ * sga_query_context_node's at `now`, with the rotations of sga_query_nodes.  parent is the birth parent's resource
+ * id when the pair (parent, context) has a DefaultNode born strictly before this one, else SGA_PARENT_ENTRANCE:
+ * Context.getLastNode's fallback to the EntranceNode when the enclosing entry has no node (Context.java:180-186,
+ * CtEntry.java:157-159).  The rule makes the edges a forest for any input: a self-parent and a parent born later
+ * both fall to the EntranceNode.  More rows than cap: SGA_ERANGE, *n_out = the number needed, the first cap rows
+ * in `out` unsorted.  No contexts registered: SGA_OK, 0 rows.  EntranceNode and Constants.ROOT values are sums
+ * over these rows (EntranceNode.java:45-126), formed by the host. */
+int sga_query_tree(sga_engine *e, int64_t now, sga_tree_row *out, size_t cap, size_t *n_out);
 
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {

@@ -109,6 +109,13 @@ class SgaNodeRow(C.Structure):
                 ("view", SgaNodeView)]
 
 
+class SgaTreeRow(C.Structure):
+    _fields_ = [("resource", C.c_uint32), ("context", C.c_uint32), ("parent", C.c_uint32), ("reserved", C.c_uint32),
+                ("view", SgaNodeView)]
+
+
+SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
+
 # sga_query_nodes: the node table, and the flag of clusterNode?type=notZero
 SGA_NODES_RESOURCE, SGA_NODES_ORIGIN, SGA_NODES_CONTEXT = 0, 1, 2
 SGA_NODES_NOT_ZERO = 1
@@ -225,6 +232,14 @@ SIGNATURES = {
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "sga_query_context_node": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.POINTER(SgaNodeView)]),
+    "sga_submit_events_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sga_submit_events_tree_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sga_query_tree": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_context_nodes_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -5,11 +5,14 @@
   SimpleHttpCommandCenter (server socket, next free port)              -> SimpleHttpCommandCenter
   CommandHandler implementations of sentinel-transport-common          -> CommandCenter's handlers:
       version, api, getRules, setRules, clusterNode, cnode, origin, systemStatus, metric
-  and of the parameter-flow extension: getParamFlowRules, setParamFlowRules.
+  and of the parameter-flow extension: getParamFlowRules, setParamFlowRules;
+      tree, jsonTree over a sentinel that records the invocation tree (LocalSentinel(tree=True)).
 
 The read commands rest on LocalSentinel.query_nodes (sga_query_nodes: one kernel launch per command).  Where the
-reference iterates a HashMap of resources or origins, rows come in ascending id (parity-unpinned: DESIGN.md).
-Not served: tree / jsonTree, getSwitch / setSwitch, the cluster-mode commands, AuthoritySlot's rules.
+reference iterates a HashMap of resources or origins, rows come in ascending id (parity-unpinned: DESIGN.md); so do
+a tree node's children, where it iterates a HashSet.  tree and jsonTree rest on LocalSentinel.invocation_tree
+(sga_query_tree: one launch) and are registered only over a sentinel whose `tree` attribute is true.
+Not served: getSwitch / setSwitch, the cluster-mode commands, AuthoritySlot's rules.
 """
 import dataclasses
 import json
@@ -17,6 +20,7 @@ import math
 import socket
 import threading
 import time
+import uuid
 from typing import Callable, Dict, List, Optional, Tuple
 from urllib.parse import unquote_plus
 
@@ -318,6 +322,54 @@ def node_vo(name: str, v: NodeView, timestamp: int) -> dict:
             "totalQps": _j_long(v.pass_qps + v.block_qps)}
 
 
+TREE_LEGEND = ("t:threadNum  pq:passQps  bq:blockQps  tq:totalQps  rt:averageRt  prq: passRequestQps 1mp:1m-pass "
+               "1mb:1m-block 1mt:1m-total")
+
+
+def format_tree(tree, id: Optional[str] = None) -> str:
+    """FetchTreeCommandHandler over LocalSentinel.invocation_tree's ROOT: a preorder walk, `level` dashes before
+    each line, an EntranceNode's line (ROOT is one) prefixed.  With id, the walk starts at level 0 from the ROOT
+    child whose name equals id, or, when none does, from every ROOT child whose name contains it."""
+    out: List[str] = []
+
+    def visit(level: int, node) -> None:
+        v = node.view
+        total = v.total_pass + v.total_block
+        out.append("-" * level + ("EntranceNode: " if node.entrance else "") +
+                   "%s(t:%s pq:%s bq:%s tq:%s rt:%s prq:%s 1mp:%s 1mb:%s 1mt:%s)" % tuple(_jstr(x) for x in (
+                       node.name, v.cur_thread_num, v.pass_qps, v.block_qps, v.pass_qps + v.block_qps, v.avg_rt,
+                       v.success_qps, total - v.total_block, v.total_block, total)) + "\n")
+        for child in node.children:
+            visit(level + 1, child)
+
+    if id is None:
+        visit(0, tree)
+    else:
+        exact = next((c for c in tree.children if c.name == id), None)
+        for c in ([exact] if exact is not None else [c for c in tree.children if id in c.name]):
+            visit(0, c)
+    return "".join(out) + "\r\n\r\n" + TREE_LEGEND + "\r\n"
+
+
+def tree_node_vos(tree, timestamp: int, new_id: Callable[[], object] = uuid.uuid4) -> List[dict]:
+    """FetchJsonTreeCommandHandler: NodeVo.fromDefaultNode of every node in preorder from ROOT -- node_vo's
+    counters plus id (str(new_id()): a random UUID) and parentId (the parent's id; null for ROOT, and fastjson
+    leaves nulls out), keys in alphabetical order."""
+    out: List[dict] = []
+
+    def visit(node, parent_id: Optional[str]) -> None:
+        vo = node_vo(node.name, node.view, timestamp)
+        vo["id"] = str(new_id())
+        if parent_id is not None:
+            vo["parentId"] = parent_id
+        out.append(dict(sorted(vo.items())))
+        for child in node.children:
+            visit(child, vo["id"])
+
+    visit(tree, None)
+    return out
+
+
 def format_system_status(v: NodeView) -> str:
     """FetchSystemStatusCommandHandler: a HashMap of five keys, written in that HashMap's iteration order."""
     return to_json({"b": v.block_qps, "r": v.avg_rt, "t": v.cur_thread_num, "qps": v.pass_qps,
@@ -358,6 +410,10 @@ class CommandCenter:
                 ("metric", "get and aggregate metrics, accept param: startTime={startTime}&endTime={endTime}"
                            "&maxLines={maxLines}&identify={resourceName}", self._metric)):
             self.register(name, desc, fn)
+        if getattr(sentinel, "tree", False):  # the sentinel records the invocation tree's edges
+            self.register("tree", "get metrics in tree mode, use id to specify detailed tree root", self._tree)
+            self.register("jsonTree", "get tree node VO start from root node", self._json_tree)
+        self.new_id: Callable[[], object] = uuid.uuid4  # NodeVo's UUID.randomUUID()
 
     def register(self, name: str, desc: str, fn: Callable[[Dict[str, str]], str]) -> None:
         """@CommandMapping(name, desc) on a handler: fn(params) returns the text or raises ValueError (ofFailure)."""
@@ -445,6 +501,13 @@ class CommandCenter:
             return "Not find cNode with id " + name
         origins = self.s.origin_node_views(rid, self.clock()) if self.s.origins else []
         return format_origin(self.s.resources[rid], origins)
+
+    def _tree(self, p):
+        return format_tree(self.s.invocation_tree(self.clock()), p.get("id"))
+
+    def _json_tree(self, p):
+        now = self.clock()
+        return to_json(tree_node_vos(self.s.invocation_tree(now), now, self.new_id))
 
     def _system_status(self, p):
         return format_system_status(self.s.nodes(self.clock(), [ENTRY_NODE])[0][1])

@@ -2456,6 +2456,14 @@ int sga_submit_events_ctx(sga_engine *e, const uint8_t *kind, const uint32_t *re
                           const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
                           const uint32_t *origin, const uint32_t *context, size_t n, const uint64_t *param_values,
                           size_t n_values, int8_t *decision, int32_t *wait_ms) {
+    return sga_submit_events_tree(e, kind, resource, ts, acquire, flags, rt, param, origin, context, nullptr, n,
+                                  param_values, n_values, decision, wait_ms);
+}
+
+int sga_submit_events_tree(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
+                           const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
+                           const uint32_t *origin, const uint32_t *context, const uint32_t *parent, size_t n,
+                           const uint64_t *param_values, size_t n_values, int8_t *decision, int32_t *wait_ms) {
     if (n && (!kind || !resource || !ts || !acquire || !decision)) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
@@ -2479,7 +2487,7 @@ int sga_submit_events_ctx(sga_engine *e, const uint8_t *kind, const uint32_t *re
             }
         }
         return g.flow.submit(kind, resource, ts, acquire, flags, rt, param, n, decision, wait_ms, param_values,
-                             n_values, origin, context);
+                             n_values, origin, context, parent);
     });
 }
 
@@ -2507,6 +2515,17 @@ int sga_submit_events_ctx_device(sga_engine *e, const uint8_t *d_kind, const uin
                                  const int64_t *d_rt, const uint64_t *d_param, const uint32_t *d_origin,
                                  const uint32_t *d_context, size_t n, const uint64_t *d_param_values, size_t n_values,
                                  int8_t *d_decision, int32_t *d_wait_ms, void *hip_stream) {
+    return sga_submit_events_tree_device(e, d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param,
+                                         d_origin, d_context, nullptr, n, d_param_values, n_values, d_decision,
+                                         d_wait_ms, hip_stream);
+}
+
+int sga_submit_events_tree_device(sga_engine *e, const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base,
+                                  const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags,
+                                  const int64_t *d_rt, const uint64_t *d_param, const uint32_t *d_origin,
+                                  const uint32_t *d_context, const uint32_t *d_parent, size_t n,
+                                  const uint64_t *d_param_values, size_t n_values, int8_t *d_decision,
+                                  int32_t *d_wait_ms, void *hip_stream) {
     if (n && (!d_kind || !d_resource || !d_ts_off || !d_acquire || !d_decision)) return SGA_EINVAL;
     if (ts_base < 0) return SGA_EINVAL;  // LeapArray.currentWindow(t < 0) returns null
     return guarded(e, [&](Engine &g) {
@@ -2537,7 +2556,7 @@ int sga_submit_events_ctx_device(sga_engine *e, const uint8_t *d_kind, const uin
         hipStream_t s = g.enter_stream(hip_stream);
         const int rc = g.flow.submit_device(d_kind, d_resource, ts_base, d_ts_off, d_acquire, d_flags, d_rt, d_param, n,
                                             d_param_values, n_values, d_decision, d_wait_ms, s, d_origin,
-                                            d_context);
+                                            d_context, d_parent);
         g.leave_stream(s);
         return rc;
     });
@@ -2562,6 +2581,13 @@ int sga_query_nodes(sga_engine *e, int table, const uint32_t *resources, size_t 
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
         return g.flow.query_nodes(table, resources, n, now, flags, out, cap, n_out);
+    });
+}
+
+int sga_query_tree(sga_engine *e, int64_t now, sga_tree_row *out, size_t cap, size_t *n_out) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.query_tree(now, out, cap, n_out);
     });
 }
 

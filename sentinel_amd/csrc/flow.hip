@@ -1512,10 +1512,12 @@ struct PairIds {
 
 // Claim pass: every kind 0 / 2 / 3 event with an id finds or claims its pair's slot (the CAS pattern of
 // ptab_get) and lowers the pair's birth to its own sequence; the slot's winner takes the next node record.  A
-// full table or an id past n_ids refuses the chunk (ctl[0]; device entry: the gate).
+// full table or an id past n_ids refuses the chunk (ctl[0]; device entry: the gate), and so does, with a parent
+// array (null: none), an event that may create a DefaultNode under a parent that names no resource.
 __global__ __launch_bounds__(kT) void k_oclaim(PairTabs pt, PairIds ids, const uint8_t *__restrict__ kind,
                                                const uint32_t *__restrict__ resource, uint32_t n, uint32_t nres,
-                                               uint64_t seq_base, uint32_t *gate) {
+                                               uint64_t seq_base, uint32_t *gate,
+                                               const uint32_t *__restrict__ parent) {
     const uint32_t i = blockIdx.x * kT + threadIdx.x;
     uint32_t bad = 0;
     // a chunk k_lgate already refused claims nothing (this pass's own refusals carry kGateFull or kGateOrigin)
@@ -1532,6 +1534,8 @@ __global__ __launch_bounds__(kT) void k_oclaim(PairTabs pt, PairIds ids, const u
             if (o > os.n_ids) {
                 bad |= kPairBadId;
             } else if (o && creates) {
+                if (pk == kPairContext && parent && parent[i] >= nres && parent[i] != SGA_PARENT_ENTRANCE)
+                    bad |= kPairBadId;
                 const unsigned long long k = pair_key(r, o);
                 uint32_t h = pair_home(os, k);
                 for (uint32_t step = 0; step <= os.mask; ++step, h = (h + 1) & os.mask) {
@@ -1581,6 +1585,22 @@ __global__ __launch_bounds__(kT) void k_orollback(PairTabs pt, uint32_t kinds, u
         if (os.born[h] != kPairUnborn && os.born[h] >= seq_base) os.born[h] = kPairUnborn;
         if (os.idx[h] == kPairNone) os.key[h] = k | kPairDead;
     }
+}
+
+// Birth pass (chunks with a parent array, after the claim pass has lowered every birth): the event whose sequence
+// is its slot's birth is the pair's first in arrival order, wherever it sits in the grid, and the only one of the
+// chunk (sequences are unique); it records the entry that encloses it as the DefaultNode's parent, the edge of
+// ((DefaultNode) context.getLastNode()).addChild(node) (NodeSelectorSlot.java:158-177: taken at creation only).  A
+// pair born in an earlier chunk has born < seq_base and keeps its word; a refused chunk's pairs are unborn again
+// (k_orollback) and write theirs at their real birth.
+__global__ __launch_bounds__(kT) void k_obirth(PairState os, const uint32_t *__restrict__ slot,
+                                               const uint32_t *__restrict__ parent, uint32_t n, uint64_t seq_base,
+                                               const uint32_t *gate) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n || (gate && (*gate & kGateBad))) return;  // a refused chunk: its slots may not even be written
+    const uint32_t h = slot[i];
+    if (h == kPairNone || h > os.mask) return;
+    if (os.born[h] == seq_base + i) os.parent[h] = parent[i];
 }
 
 // small chunks: one lane, arrival order
@@ -6170,38 +6190,11 @@ __device__ __forceinline__ int64_t wave_sum64(int64_t v) {
     return v;
 }
 
-__global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a, int64_t max_rt, int64_t now,
-                                                                 sga_node_row *out, uint32_t cap, uint32_t *count) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = blockIdx.x * kViewsWaves + (threadIdx.x >> 6);  // wave-uniform
-    // which node, if any (the same in every lane of the wave)
-    bool live = w < a.ncand;
-    uint32_t rec = 0, resource = 0, other = 0;
-    if (live && a.pair.node) {
-        const unsigned long long k = a.pair.key[w];
-        live = k != 0 && !(k & kPairDead) && a.pair.born[w] != kPairUnborn;
-        if (live) {
-            resource = (uint32_t)(k >> 32) - 1u;
-            other = (uint32_t)k;
-            rec = a.pair.idx[w];
-            if (a.filt) {
-                uint32_t lo = 0, hi = a.nfilt;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) / 2;
-                    if (a.filt[mid] < resource) lo = mid + 1;
-                    else hi = mid;
-                }
-                live = lo < a.nfilt && a.filt[lo] == resource;
-            }
-            live = live && rec < a.pair.max_nodes;
-        }
-    } else if (live) {
-        rec = a.list ? a.list[w] : w;
-        resource = rec == a.nres ? SGA_ENTRY_NODE : rec;
-        live = rec <= a.nres;
-    }
-    int64_t *node = a.node + (size_t)rec * kNodeWords;
-    if (live && !a.pair.node && !a.list) live = node[kNodeEntered] != 0;
+// The per-node part of the bulk view kernels (k_node_views, k_tree_rows), as described above: called by every thread
+// of the block with its wave's node (it holds the block's one barrier), `live` wave-uniform.  True in lane 0 of a
+// live node, whose sums are then in `s` and whose entered word in `entered`.
+__device__ __forceinline__ bool node_wave_sums(int64_t *node, bool live, uint32_t lane, int64_t max_rt, int64_t now,
+                                               NodeSums &s, int64_t &entered) {
     if (live && lane == 0) {
         bool det;
         sec_current(node, now, max_rt);
@@ -6209,14 +6202,13 @@ __global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a
         bor_current(node, now, &det);
     }
     __syncthreads();  // every wave of the block arrives: the rotations above are visible to the wave's other lanes
-    if (!live) return;
+    if (!live) return false;
 
     int64_t b[kMB];
     b[0] = kAbsent;
 #pragma unroll
     for (int f = 1; f < kMB; ++f) b[f] = 0;
-    NodeSums s;
-    int64_t entered = 0;
+    entered = 0;
     s.threads = s.waiting = 0;
     s.prev_pass = s.prev_block = 0.0;
     if (lane < 62) {
@@ -6261,7 +6253,44 @@ __global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a
     s.prev_pass = __shfl(s.prev_pass, 62, 64);
     s.prev_block = __shfl(s.prev_block, 62, 64);
     entered = __shfl(entered, 62, 64);
-    if (lane) return;
+    return lane == 0;
+}
+
+__global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a, int64_t max_rt, int64_t now,
+                                                                 sga_node_row *out, uint32_t cap, uint32_t *count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = blockIdx.x * kViewsWaves + (threadIdx.x >> 6);  // wave-uniform
+    // which node, if any (the same in every lane of the wave)
+    bool live = w < a.ncand;
+    uint32_t rec = 0, resource = 0, other = 0;
+    if (live && a.pair.node) {
+        const unsigned long long k = a.pair.key[w];
+        live = k != 0 && !(k & kPairDead) && a.pair.born[w] != kPairUnborn;
+        if (live) {
+            resource = (uint32_t)(k >> 32) - 1u;
+            other = (uint32_t)k;
+            rec = a.pair.idx[w];
+            if (a.filt) {
+                uint32_t lo = 0, hi = a.nfilt;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) / 2;
+                    if (a.filt[mid] < resource) lo = mid + 1;
+                    else hi = mid;
+                }
+                live = lo < a.nfilt && a.filt[lo] == resource;
+            }
+            live = live && rec < a.pair.max_nodes;
+        }
+    } else if (live) {
+        rec = a.list ? a.list[w] : w;
+        resource = rec == a.nres ? SGA_ENTRY_NODE : rec;
+        live = rec <= a.nres;
+    }
+    int64_t *node = a.node + (size_t)rec * kNodeWords;
+    if (live && !a.pair.node && !a.list) live = node[kNodeEntered] != 0;
+    NodeSums s;
+    int64_t entered;
+    if (!node_wave_sums(node, live, lane, max_rt, now, s, entered)) return;
     if ((a.flags & SGA_NODES_NOT_ZERO) && !(s.min_pass + s.min_block > 0)) return;
     const uint32_t k = atomicAdd(count, 1u);
     if (k >= cap) return;
@@ -6272,6 +6301,49 @@ __global__ __launch_bounds__(64 * kViewsWaves) void k_node_views(NodeViewsArgs a
     row.reserved = 0;
     row.view = node_view_form(s);
     out[k] = row;
+}
+
+// The invocation tree's rows (sga_query_tree): one wave per slot of the context table, the views formed as in
+// k_node_views.  Lane 0 also resolves the DefaultNode's edge: the birth parent p stands when the pair (p, context)
+// has a DefaultNode born strictly before this one, else the node hangs under its EntranceNode -- what
+// Context.getLastNode answers when the enclosing entry has no node (Context.java:180-186, CtEntry.java:157-159).
+// Births are unique sequences, so a self-parent and a parent born later both fall to the EntranceNode and the
+// edges form a forest whatever the parents were.
+__global__ __launch_bounds__(64 * kViewsWaves) void k_tree_rows(PairState os, uint32_t nslots, int64_t max_rt,
+                                                                int64_t now, sga_tree_row *out, uint32_t cap,
+                                                                uint32_t *count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = blockIdx.x * kViewsWaves + (threadIdx.x >> 6);  // wave-uniform
+    bool live = w < nslots;
+    unsigned long long k = 0;
+    uint32_t rec = 0;
+    if (live) {
+        k = os.key[w];
+        live = k != 0 && !(k & kPairDead) && os.born[w] != kPairUnborn;
+        if (live) {
+            rec = os.idx[w];
+            live = rec < os.max_nodes;
+        }
+    }
+    if (!live) rec = 0;
+    NodeSums s;
+    int64_t entered;
+    if (!node_wave_sums(os.node + (size_t)rec * kNodeWords, live, lane, max_rt, now, s, entered)) return;
+    const uint32_t context = (uint32_t)k;
+    uint32_t parent = os.parent[w];
+    if (parent != SGA_PARENT_ENTRANCE) {
+        const uint32_t h = pair_find(os, pair_key(parent, context));
+        if (h == kPairNone || os.born[h] >= os.born[w]) parent = SGA_PARENT_ENTRANCE;  // unborn is the largest
+    }
+    const uint32_t q = atomicAdd(count, 1u);
+    if (q >= cap) return;
+    sga_tree_row row;
+    row.resource = (uint32_t)(k >> 32) - 1u;
+    row.context = context;
+    row.parent = parent;
+    row.reserved = 0;
+    row.view = node_view_form(s);
+    out[q] = row;
 }
 
 __global__ void k_init_nodes(int64_t *node, uint32_t n, int64_t max_rt) {
@@ -7459,7 +7531,8 @@ int FlowEngine::ensure_scratch() {
 int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire,
                              const uint8_t *flags, const int64_t *rt, const uint64_t *param, const uint32_t *ts_off,
                              int64_t lo, uint32_t m, int8_t *decision, int32_t *wait_ms, const uint64_t *pvals,
-                             size_t npvals, const uint32_t *origin, const uint32_t *context) {
+                             size_t npvals, const uint32_t *origin, const uint32_t *context,
+                             const uint32_t *parent) {
     auto a8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
     const size_t o_kind = 0, o_flags = a8(o_kind + kSmallEvents), o_res = a8(o_flags + kSmallEvents),
                  o_ts = o_res + 4 * kSmallEvents, o_acq = o_ts + 4 * kSmallEvents, o_rt = o_acq + 4 * kSmallEvents,
@@ -7505,9 +7578,14 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
             ids[k] = ptab[k].ids.p;
         }
     const bool pairs = origin || context;
+    const uint32_t *dpar_ids = nullptr;  // the enclosing entries, for the DefaultNodes the chunk creates
+    if (parent && context) {
+        dpar_ids = ptab[kPairContext].parents.p;
+        SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent, 4 * (size_t)m, hipMemcpyHostToDevice, stream));
+    }
     // pair nodes exist ahead of every check; a full table refuses the chunk
     if (pairs)
-        if (const int rc = pair_claim(dk, dres, ids, m, nullptr, stream)) return rc;
+        if (const int rc = pair_claim(dk, dres, ids, m, nullptr, stream, dpar_ids)) return rc;
     pair_ctx(ids, stream);
     lru_prepare(dk, dres, dfl, dpar, dvals, m, stream);  // CacheMap capacity
     FlowScratch fs = sc;
@@ -7561,9 +7639,10 @@ FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *
 int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int64_t *ts, const int32_t *acquire,
                        const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
                        int32_t *wait_ms, const uint64_t *pvals, size_t npvals, const uint32_t *origin,
-                       const uint32_t *context) {
+                       const uint32_t *context, const uint32_t *parent) {
     if (!nres) return SGA_EINVAL;
     if (n == 0) return 0;
+    if (!context) parent = nullptr;  // only an event with a context creates a DefaultNode
     const uint32_t *hids[kPairKinds] = {origin, context}, *ids[kPairKinds] = {nullptr, nullptr};
     for (int k = 0; k < kPairKinds; ++k) {
         if (!hids[k]) continue;  // an id past the registered ones refuses the call
@@ -7572,6 +7651,11 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
             if (hids[k][i] > ptab[k].n_ids) return SGA_EINVAL;
         ids[k] = ptab[k].ids.p;
     }
+    // a parent that names no resource, on an event that may create a DefaultNode, refuses the call like a bad id
+    for (size_t i = 0; parent && i < n; ++i)
+        if (parent[i] >= nres && parent[i] != SGA_PARENT_ENTRANCE && context[i] && resource[i] < nres &&
+            kind[i] != SGA_KIND_EXIT)
+            return SGA_EINVAL;
     const bool pairs = origin || context;
     // Collection / array arguments (SGA_EV_PARAM_LIST): the value array goes to the device once;
     // chunks holding such events are replayed in arrival order by one lane (k_lseq)
@@ -7642,7 +7726,8 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                                             rt ? rt + b : nullptr, param ? param + b : nullptr, off.data(), lo,
                                             (uint32_t)m, decision + b, wait_ms ? wait_ms + b : nullptr,
                                             has_list ? pvals : nullptr, has_list ? npvals : 0,
-                                            origin ? origin + b : nullptr, context ? context + b : nullptr)) {
+                                            origin ? origin + b : nullptr, context ? context + b : nullptr,
+                                            parent ? parent + b : nullptr)) {
                 seq += m;  // a chunk that failed part-way keeps its sequence numbers (pair births)
                 return rc;
             }
@@ -7663,9 +7748,13 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         for (int k = 0; k < kPairKinds; ++k)
             if (hids[k])
                 SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k] + b, m * 4, hipMemcpyHostToDevice, stream));
+        if (parent)
+            SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent + b, m * 4, hipMemcpyHostToDevice, stream));
         // pair nodes exist ahead of every check; a full table refuses the chunk
         if (pairs)
-            if (const int rc = pair_claim(d_kind.p, d_resid.p, ids, (uint32_t)m, nullptr, stream)) return rc;
+            if (const int rc = pair_claim(d_kind.p, d_resid.p, ids, (uint32_t)m, nullptr, stream,
+                                          parent ? ptab[kPairContext].parents.p : nullptr))
+                return rc;
         SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, stream));
         // per chunk: a probe sequence that overflowed in an earlier (failed) batch must not fail
         // every later one.  A failed batch has been partly applied (its node and breaker updates
@@ -7810,7 +7899,8 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
                               const uint32_t *d_ts_off, const int32_t *d_acquire, const uint8_t *d_flags_in,
                               const int64_t *d_rt_in, const uint64_t *d_param_in, size_t n,
                               const uint64_t *d_param_values, size_t n_values, int8_t *d_decision, int32_t *d_wait,
-                              hipStream_t s, const uint32_t *d_origin_in, const uint32_t *d_context_in) {
+                              hipStream_t s, const uint32_t *d_origin_in, const uint32_t *d_context_in,
+                              const uint32_t *d_parent_in) {
     if (!nres || (d_origin_in && !ptab[kPairOrigin].n_ids) || (d_context_in && !ptab[kPairContext].n_ids))
         return SGA_EINVAL;
     const uint32_t *ids[kPairKinds] = {d_origin_in, d_context_in};
@@ -7842,7 +7932,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     hipLaunchKernelGGL(k_lgate, dim3(gb), dim3(kT), 0, s, d_kind_in, d_resource, d_acquire, flags_p, param_p, m, nres,
                        (int)sys.check, (uint64_t)(d_param_values ? n_values : 0), d_gate.p, d_param_values);
     if (pairs)  // pair nodes exist ahead of every check; a full table or a bad id closes the gate
-        if (const int rc = pair_claim(d_kind_in, d_resource, ids, m, d_gate.p, s)) return rc;
+        if (const int rc = pair_claim(d_kind_in, d_resource, ids, m, d_gate.p, s, d_parent_in)) return rc;
     pair_ctx(ids, s);
     lru_prepare(d_kind_in, d_resource, flags_p, param_p, d_param_values, m, s);  // CacheMap capacity
     FlowState st = state();
@@ -8027,6 +8117,31 @@ int FlowEngine::query_nodes(int table, const uint32_t *resources, size_t n, int6
     return 0;
 }
 
+int FlowEngine::query_tree(int64_t now, sga_tree_row *out, size_t cap, size_t *n_out) {
+    if (now < 0 || !n_out || (cap && !out)) return SGA_EINVAL;
+    *n_out = 0;
+    const PairTable &t = ptab[kPairContext];
+    if (!t.n_ids) return 0;
+    const uint32_t dcap = (uint32_t)std::min<size_t>(cap, t.max_nodes);
+    if (d_trows.n < std::max<size_t>(dcap, 1)) d_trows.alloc(std::max<size_t>(dcap, 1));
+    if (d_vlist.n < 1) d_vlist.alloc(1);
+    SGA_HIP_CHECK(hipMemsetAsync(d_vlist.p, 0, 4, stream));
+    hipLaunchKernelGGL(k_tree_rows, dim3((t.slots + kViewsWaves - 1) / kViewsWaves), dim3(64 * kViewsWaves), 0, stream,
+                       pstate().t[kPairContext], t.slots, (int64_t)cfg.statistic_max_rt, now, d_trows.p, dcap,
+                       d_vlist.p);
+    SGA_HIP_CHECK(hipGetLastError());
+    uint32_t cnt = 0;
+    SGA_HIP_CHECK(hipMemcpyAsync(&cnt, d_vlist.p, 4, hipMemcpyDeviceToHost, stream));
+    if (dcap) SGA_HIP_CHECK(hipMemcpyAsync(out, d_trows.p, (size_t)dcap * sizeof(sga_tree_row), hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    *n_out = cnt;
+    if (cnt > cap) return SGA_ERANGE;
+    std::sort(out, out + cnt, [](const sga_tree_row &x, const sga_tree_row &y) {
+        return x.context != y.context ? x.context < y.context : x.resource < y.resource;
+    });
+    return 0;
+}
+
 // ---- pair nodes: caller origins (kPairOrigin) and contexts (kPairContext)
 int FlowEngine::set_pairs(int kind, uint32_t n, uint32_t max_nodes) {
     if (!nres || n == 0 || n >= SGA_LIMIT_OTHER) return SGA_EINVAL;
@@ -8044,6 +8159,11 @@ int FlowEngine::set_pairs(int kind, uint32_t n, uint32_t max_nodes) {
     t.idx.alloc(slots);
     t.ids.alloc(cap);
     t.slot.alloc(cap);
+    if (kind == kPairContext) {  // the invocation tree's edges: every pair under its EntranceNode until told otherwise
+        t.parent.alloc(slots);
+        t.parents.alloc(cap);
+        SGA_HIP_CHECK(hipMemsetAsync(t.parent.p, 0xFF, t.parent.bytes(), stream));
+    }
     const bool both = ptab[kind ^ 1].n_ids != 0;
     if (!d_pctl.p) {
         d_pctl.alloc(8);
@@ -8083,7 +8203,8 @@ PairTabs FlowEngine::pstate() const {
     for (int k = 0; k < kPairKinds; ++k) {
         const PairTable &t = ptab[k];
         if (!t.n_ids) continue;
-        pt.t[k] = PairState{t.node.p, t.key.p, t.born.p, t.idx.p, d_pctl.p + 2 + k, t.slots - 1, t.max_nodes, t.n_ids};
+        pt.t[k] = PairState{t.node.p, t.key.p, t.born.p, t.idx.p, d_pctl.p + 2 + k, t.slots - 1, t.max_nodes, t.n_ids,
+                            t.parent.p};
     }
     pt.ctl = d_pctl.p;
     pt.base1 = ptab[kPairOrigin].max_nodes;
@@ -8107,25 +8228,37 @@ void FlowEngine::pair_ctx(const uint32_t *const ids[kPairKinds], hipStream_t s) 
 }
 
 int FlowEngine::pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
-                           uint32_t m, uint32_t *gate, hipStream_t s) {
+                           uint32_t m, uint32_t *gate, hipStream_t s, const uint32_t *parent) {
     const PairTabs pt = pstate();
     const PairIds pi{{ids[0], ids[1]}, {ptab[0].slot.p, ptab[1].slot.p}};
     const uint32_t kinds = (ids[0] ? 1u : 0u) | (ids[1] ? 2u : 0u);
     uint32_t rslots = 0;
     for (int k = 0; k < kPairKinds; ++k)
         if (ids[k]) rslots = std::max(rslots, ptab[k].slots);
+    if (!ids[kPairContext]) parent = nullptr;  // no event of the chunk creates a DefaultNode
+    // the birth pass: only for a chunk that carries parents, once every birth of the chunk is known
+    auto births = [&]() {
+        if (!parent) return;
+        hipLaunchKernelGGL(k_obirth, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt.t[kPairContext],
+                           ptab[kPairContext].slot.p, parent, m, (uint64_t)seq, gate);
+    };
     SGA_HIP_CHECK(hipMemsetAsync(d_pctl.p, 0, 8, s));  // the chunk's error bits and long segments
     hipLaunchKernelGGL(k_oclaim, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, kind, resource, m, nres,
-                       (uint64_t)seq, gate);
+                       (uint64_t)seq, gate, parent);
     if (gate) {  // device entry: the gate refuses the chunk, k_lfail reports it
         hipLaunchKernelGGL(k_orollback, dim3((rslots + kT - 1) / kT), dim3(kT), 0, s, pt, kinds, (uint64_t)seq, gate);
+        births();
         SGA_HIP_CHECK(hipGetLastError());
         return 0;
     }
     uint32_t err = 0;
     SGA_HIP_CHECK(hipMemcpyAsync(&err, d_pctl.p, 4, hipMemcpyDeviceToHost, s));
     SGA_HIP_CHECK(hipStreamSynchronize(s));
-    if (!err) return 0;
+    if (!err) {
+        births();
+        SGA_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(k_orollback, dim3((rslots + kT - 1) / kT), dim3(kT), 0, s, pt, kinds, (uint64_t)seq, nullptr);
     SGA_HIP_CHECK(hipGetLastError());
     SGA_HIP_CHECK(hipStreamSynchronize(s));

@@ -141,7 +141,10 @@ struct SysDev {
 // DefaultNode and on the ClusterNode.  An open-addressing table maps the pair to its node
 // record: key[h] = (resource + 1) << 32 | id (0: empty; bit 63: a slot a refused chunk left without a
 // record, matched by nobody), idx[h] = the record, born[h] = the event sequence of the pair's first kind 0 / 2 /
-// 3 event (~0: reserved by a refused chunk, not created).
+// 3 event (~0: reserved by a refused chunk, not created).  The context table keeps one more word per slot, parent[h]:
+// the resource id of the entry that enclosed the pair's first event (context.getLastNode() when NodeSelectorSlot
+// created the DefaultNode and called addChild, NodeSelectorSlot.java:158-177), SGA_PARENT_ENTRANCE for an
+// outermost one and for every pair born through an entry point without a parent array.
 struct PairState {
     int64_t *node;             // max_nodes records of kNodeWords words, initialised like a resource's node;
                                // null: this kind of pair is not registered
@@ -149,6 +152,7 @@ struct PairState {
     uint32_t *idx;
     uint32_t *cnt;             // records handed out
     uint32_t mask, max_nodes, n_ids;
+    uint32_t *parent;          // context table only (null in the origin table): the birth parent per slot
 };
 constexpr int kPairOrigin = 0, kPairContext = 1, kPairKinds = 2;
 constexpr uint32_t kPairNone = 0xFFFFFFFFu;
@@ -402,7 +406,7 @@ struct FlowEngine {
     int submit(const uint8_t *kind, const uint32_t *resource, const int64_t *ts, const int32_t *acquire,
                const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
                int32_t *wait_ms, const uint64_t *pvals = nullptr, size_t npvals = 0,
-               const uint32_t *origin = nullptr, const uint32_t *context = nullptr);
+               const uint32_t *origin = nullptr, const uint32_t *context = nullptr, const uint32_t *parent = nullptr);
     FlowScratch special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
                                 const uint64_t *d_param_in, const uint64_t *d_pvals, const uint32_t *d_resource_in);
     DevBuf<uint64_t> d_pvals;  // values of Collection / array arguments (SGA_EV_PARAM_LIST)
@@ -416,18 +420,21 @@ struct FlowEngine {
     int submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire, const uint8_t *flags,
                      const int64_t *rt, const uint64_t *param, const uint32_t *ts_off, int64_t lo, uint32_t m,
                      int8_t *decision, int32_t *wait_ms, const uint64_t *pvals, size_t npvals,
-                     const uint32_t *origin = nullptr, const uint32_t *context = nullptr);
+                     const uint32_t *origin = nullptr, const uint32_t *context = nullptr,
+                     const uint32_t *parent = nullptr);
     int submit_device(const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base, const uint32_t *d_ts_off,
                       const int32_t *d_acquire, const uint8_t *d_flags, const int64_t *d_rt_in,
                       const uint64_t *d_param_in, size_t n, const uint64_t *d_param_values, size_t n_values,
                       int8_t *d_decision, int32_t *d_wait, hipStream_t s, const uint32_t *d_origin = nullptr,
-                      const uint32_t *d_context = nullptr);
+                      const uint32_t *d_context = nullptr, const uint32_t *d_parent = nullptr);
     // pair nodes (PairState): a kind is off until set_pairs, and for every call that passes no id array of it
     struct PairTable {
         uint32_t n_ids = 0, max_nodes = 0, slots = 0;
         DevBuf<int64_t> node;
         DevBuf<unsigned long long> key, born;
         DevBuf<uint32_t> idx, ids, slot;  // ids: the host entries' copy of the chunk's array
+        DevBuf<uint32_t> parent, parents; // context table: the birth parent per slot; the host entries' copy of
+                                          // the chunk's parent array
     } ptab[kPairKinds];
     DevBuf<uint32_t> d_pctl;   // [0] error bits [1] long segments [2 + kind] records handed out
     DevBuf<uint32_t> d_olong;
@@ -448,9 +455,10 @@ struct FlowEngine {
     int set_pairs(int kind, uint32_t n, uint32_t max_nodes);
     PairTabs pstate() const;
     // the claim pass of a chunk (ahead of every check): the chunk's pairs find or claim their records.  Host
-    // entry (gate null): waits, SGA_ENOMEM when a table is full -- the chunk's claims are then taken back
+    // entry (gate null): waits, SGA_ENOMEM when a table is full -- the chunk's claims are then taken back.
+    // parent (device, may be null): the chunk's enclosing resources; the pairs the chunk creates record theirs
     int pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds], uint32_t m,
-                   uint32_t *gate, hipStream_t s);
+                   uint32_t *gate, hipStream_t s, const uint32_t *parent = nullptr);
     // the statistics pass of a chunk, after its decisions (seq: one lane in arrival order, small chunks)
     void pair_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
                     const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
@@ -458,6 +466,9 @@ struct FlowEngine {
                     hipStream_t s);
     int query_pair(int kind, uint32_t resource, uint32_t id, int64_t now, sga_node_view *out);
     int pair_nodes_of(int kind, uint32_t resource, uint32_t *ids, size_t cap, size_t *n);
+    // sga_query_tree: k_tree_rows over the context table, rows sorted by (context, resource)
+    DevBuf<sga_tree_row> d_trows;
+    int query_tree(int64_t now, sga_tree_row *out, size_t cap, size_t *n_out);
     int device_status();  // sticky error of the device entry since the last call (host wait)
     int ensure_scratch();
     DevBuf<uint32_t> d_gate;  // [0] gate word of the running chunk, [1] sticky error bits

@@ -18,6 +18,9 @@ Same names and argument meaning as the Java API the engine replaces:
   ClusterBuilderSlot.getClusterNodeMap, getOriginCountMap read whole (the command center's clusterNode, cnode,
                                   origin) -> LocalSentinel.nodes / origin_node_views / default_node_views /
                                   nodes_device (sga_query_nodes: one launch for any number of nodes)
+  NodeSelectorSlot's addChild edge, EntranceNode, Constants.ROOT (CORE/node/EntranceNode.java:45-126) as the
+                                  command center's tree / jsonTree walk them -> the `parent` of entry / submit on a
+                                  LocalSentinel(tree=True), LocalSentinel.tree_rows / invocation_tree
   FlowRuleManager.getRules and its siblings -> the managers' get_rules
 BlockException subclasses as in CORE/slots/block/BlockException.java and its subclasses.
 
@@ -33,7 +36,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import SgaDegradeRule, SgaFlowRule, SgaNodeView, SgaParamRule, check
+from ._lib import SGA_PARENT_ENTRANCE, SgaConfig, SgaDegradeRule, SgaFlowRule, SgaNodeView, SgaParamRule, check
 from .cluster import Engine  # noqa: F401  (one engine serves both paths)
 from .rules import DegradeRule, FlowRule, ParamFlowRule, RuleConstant  # noqa: F401
 
@@ -151,6 +154,47 @@ NODE_ROW_DTYPE = np.dtype([("resource", "<u4"), ("other", "<u4"), ("entered", "<
                           [(f, "<f8" if t is C.c_double else "<i8") for f, t in SgaNodeView._fields_])
 
 
+# one sga_tree_row (sga_query_tree): the DefaultNode's ids and resolved parent, then the NodeView fields
+TREE_ROW_DTYPE = np.dtype([("resource", "<u4"), ("context", "<u4"), ("parent", "<u4"), ("reserved", "<u4")] +
+                          [(f, "<f8" if t is C.c_double else "<i8") for f, t in SgaNodeView._fields_])
+ROOT_NAME = "machine-root"  # Constants.ROOT_ID
+
+
+@dataclass
+class TreeNode:
+    """One node of LocalSentinel.invocation_tree: Constants.ROOT, a context's EntranceNode (entrance = True for
+    both) or a DefaultNode, with its children in the order the command center walks them."""
+    name: str
+    view: NodeView
+    entrance: bool
+    children: List["TreeNode"]
+
+
+def entrance_view(children: Sequence[NodeView], statistic_max_rt: int) -> NodeView:
+    """EntranceNode's getters over its direct children in the given order (EntranceNode.java:45-126): plain
+    doubles, summed sequentially.  blockQps, successQps, passQps, totalQps, curThreadNum, blockRequest,
+    totalRequest and totalPass are sums (totalQps is pass_qps + block_qps here: integer-valued doubles, exact in
+    any order); avgRt = sum(child.avgRt * child.passQps) / (sum(child.passQps) or 1).  Every other getter reads
+    the EntranceNode's own StatisticNode, which nothing ever adds to: zeros, minRt = statistic_max_rt,
+    maxSuccessQps = 1 x sampleCount / intervalInSec = 2."""
+    total = total_qps = block_qps = success_qps = pass_qps = 0.0
+    threads = total_pass = total_block = 0
+    for c in children:
+        total += c.avg_rt * c.pass_qps
+        total_qps += c.pass_qps
+        block_qps += c.block_qps
+        success_qps += c.success_qps
+        pass_qps += c.pass_qps
+        threads += c.cur_thread_num
+        total_pass += c.total_pass
+        total_block += c.total_block
+    return NodeView(pass_qps=pass_qps, block_qps=block_qps, success_qps=success_qps, exception_qps=0.0,
+                    occupied_pass_qps=0.0, avg_rt=total / (1 if total_qps == 0 else total_qps),
+                    min_rt=float(statistic_max_rt), previous_pass_qps=0.0, total_pass=total_pass,
+                    total_block=total_block, total_success=0, total_exception=0, cur_thread_num=threads, waiting=0,
+                    max_success_qps=2.0, previous_block_qps=0.0)
+
+
 @dataclass
 class MetricNode:
     """CORE/node/metric/MetricNode.java:28-51 (one resource, one second)."""
@@ -176,10 +220,12 @@ class Entry:
     """A passed entry; exit() records RT / success (StatisticSlot.exit) and breaker completion."""
 
     def __init__(self, owner: "LocalSentinel", rid: int, create_ts: int, count: int, param: Optional[int],
-                 wait_ms: int, inbound: bool = False, args=(), origin: str = "", context: str = ""):
+                 wait_ms: int, inbound: bool = False, args=(), origin: str = "", context: str = "",
+                 parent: Optional["Entry"] = None):
         self._owner = owner
         self.origin = origin
         self.context = context
+        self.parent = parent  # the enclosing Entry (CtEntry.parent), None for an outermost one
         self.args = tuple(args)
         self.inbound = inbound
         self.rid = rid
@@ -210,13 +256,24 @@ class LocalSentinel:
     """The local slot chain (StatisticSlot, ParamFlowSlot, FlowSlot, DegradeSlot) on one engine."""
 
     def __init__(self, engine: Engine, resources: Sequence[str], origins: Optional[Sequence[str]] = None,
-                 max_origin_nodes: int = 0, contexts: Optional[Sequence[str]] = None, max_context_nodes: int = 0):
+                 max_origin_nodes: int = 0, contexts: Optional[Sequence[str]] = None, max_context_nodes: int = 0,
+                 tree: bool = False):
         """origins: the caller names events may carry (ContextUtil.enter's origin), registered up front like
         the resources; None = no origin tracking.  max_origin_nodes sizes the engine's table of (resource,
         origin) nodes (0: the engine's default).  contexts: the context names events may carry
         (ContextUtil.enter's name), registered the same way and independently; None = no DefaultNodes, no CHAIN
-        rules.  max_context_nodes sizes the table of (resource, context) DefaultNodes."""
+        rules.  max_context_nodes sizes the table of (resource, context) DefaultNodes.  tree (needs contexts):
+        submit, submit_device and entry take `parent`, the enclosing entry, and each DefaultNode keeps the parent
+        of its first entry (NodeSelectorSlot's addChild); tree_rows and invocation_tree read the result.  The
+        default context (sentinel_default_context) appears in the tree only if the caller registers that name and
+        submits its entries with that id: context 0 stays untracked."""
         self.engine = engine
+        if tree and not contexts:
+            raise ValueError("tree=True needs registered contexts")
+        self.tree = bool(tree)
+        cfg = SgaConfig()
+        _lib.load().sga_config_default(C.byref(cfg))
+        self.statistic_max_rt = int(cfg.statistic_max_rt)  # Engine creates its engine with the default
         self.resources: List[str] = list(resources)
         self.ids: Dict[str, int] = {r: i for i, r in enumerate(self.resources)}
         if len(self.ids) != len(self.resources):
@@ -259,11 +316,15 @@ class LocalSentinel:
 
     # ---- batched form: the engine's native interface
     def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None,
-               context=None):
+               context=None, parent=None):
         """Events in arrival order.  param_values: the values of Collection / array arguments
         (events flagged SGA_EV_PARAM_LIST = 16 carry param = offset << 32 | count into it).
         origin: each event's origin id (origin_id; 0 = none), on a sentinel with registered origins.
-        context: each event's context id (context_id; 0 = none), on a sentinel with registered contexts."""
+        context: each event's context id (context_id; 0 = none), on a sentinel with registered contexts.
+        parent (tree=True, with context): each event's enclosing entry's resource id, SGA_PARENT_ENTRANCE for an
+        outermost one (sga_submit_events_tree)."""
+        if parent is not None and (not self.tree or context is None):
+            raise ValueError("parent needs a LocalSentinel(tree=True) and a context array")
         k = np.ascontiguousarray(kind, dtype=np.uint8)
         r = np.ascontiguousarray(resource, dtype=np.uint32)
         t = np.ascontiguousarray(ts, dtype=np.int64)
@@ -285,6 +346,18 @@ class LocalSentinel:
             cx = np.ascontiguousarray(context, dtype=np.uint32)
             if len(cx) != n or (og is not None and len(og) != n):
                 raise ValueError("event arrays differ in length")
+            if parent is not None:
+                pa = np.ascontiguousarray(parent, dtype=np.uint32)
+                if len(pa) != n:
+                    raise ValueError("event arrays differ in length")
+                rc = _lib.load().sga_submit_events_tree(
+                    self.engine.handle, k.ctypes.data, r.ctypes.data, t.ctypes.data, a.ctypes.data,
+                    f.ctypes.data if f is not None else None, rtv.ctypes.data if rtv is not None else None,
+                    pv.ctypes.data if pv is not None else None, og.ctypes.data if og is not None else None,
+                    cx.ctypes.data, pa.ctypes.data, n, vals.ctypes.data if vals is not None and len(vals) else None,
+                    len(vals) if vals is not None else 0, dec.ctypes.data, wait.ctypes.data)
+                check(rc, self.engine.handle, "submitEvents")
+                return dec, wait
             rc = _lib.load().sga_submit_events_ctx(
                 self.engine.handle, k.ctypes.data, r.ctypes.data, t.ctypes.data, a.ctypes.data,
                 f.ctypes.data if f is not None else None, rtv.ctypes.data if rtv is not None else None,
@@ -358,20 +431,25 @@ class LocalSentinel:
         return int(d.value), int(w.value)
 
     def submit_device(self, kind, resource, ts_base, ts_off, acquire, flags=None, rt=None, param=None,
-                      param_values=None, decision=None, wait=None, stream=None, origin=None, context=None):
+                      param_values=None, decision=None, wait=None, stream=None, origin=None, context=None,
+                      parent=None):
         """submit over device tensors (torch, on the engine's GPU), asynchronous on `stream` (torch stream or
         None = the engine stream): one chunk of at most max_batch events with timestamps ts_base + ts_off.
         Returns (decision int8, wait int32) device tensors; device_status() reports a chunk the device
-        checks rejected (rc -EINVAL) or a full parameter map (rc -ENOMEM) as EngineError."""
+        checks rejected (rc -EINVAL) or a full parameter map (rc -ENOMEM) as EngineError.  parent (tree=True, with
+        context): the enclosing entries' resource ids (sga_submit_events_tree_device)."""
         import torch
+        if parent is not None and (not self.tree or context is None):
+            raise ValueError("parent needs a LocalSentinel(tree=True) and a context tensor")
         n = kind.numel()
-        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param, origin, context) if v is not None):
+        for x in (resource, ts_off, acquire) + tuple(v for v in (flags, rt, param, origin, context, parent)
+                                                     if v is not None):
             if x.numel() != n or not x.is_cuda or not x.is_contiguous():
                 raise ValueError("event tensors must be contiguous device tensors of one length")
         want = {"kind": (kind, torch.uint8), "resource": (resource, torch.int32), "ts_off": (ts_off, torch.int32),
                 "acquire": (acquire, torch.int32), "flags": (flags, torch.uint8), "rt": (rt, torch.int64),
                 "param": (param, torch.int64), "param_values": (param_values, torch.int64),
-                "origin": (origin, torch.int32), "context": (context, torch.int32)}
+                "origin": (origin, torch.int32), "context": (context, torch.int32), "parent": (parent, torch.int32)}
         for name, (x, dt) in want.items():
             if x is not None and x.element_size() != torch.empty(0, dtype=dt).element_size():
                 raise ValueError(f"{name}: element size of {dt} expected")
@@ -380,6 +458,14 @@ class LocalSentinel:
         if wait is None:
             wait = torch.empty(n, dtype=torch.int32, device=kind.device)
         ptr = (lambda x: x.data_ptr() if x is not None else None)
+        if parent is not None:  # the _ctx entry below with the enclosing entry per event
+            rc = _lib.load().sga_submit_events_tree_device(
+                self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
+                acquire.data_ptr(), ptr(flags), ptr(rt), ptr(param), ptr(origin), context.data_ptr(),
+                parent.data_ptr(), n, ptr(param_values), param_values.numel() if param_values is not None else 0,
+                decision.data_ptr(), wait.data_ptr(), stream.cuda_stream if stream is not None else None)
+            check(rc, self.engine.handle, "submitEventsDevice")
+            return decision, wait
         if context is not None:  # context (and origin) ids per event; a full table: device_status, rc -ENOMEM
             rc = _lib.load().sga_submit_events_ctx_device(
                 self.engine.handle, kind.data_ptr(), resource.data_ptr(), int(ts_base), ts_off.data_ptr(),
@@ -410,10 +496,18 @@ class LocalSentinel:
 
     # ---- SphU-style single entry
     def entry(self, resource: str, now: int, batch_count: int = 1, prioritized: bool = False, args=(),
-              entry_type: str = "OUT", origin: str = "", context: str = "") -> Entry:
+              entry_type: str = "OUT", origin: str = "", context: str = "",
+              parent: Optional[Entry] = None) -> Entry:
         """SphU.entry(resource, entryType, batchCount, args); entry_type "IN" marks inbound traffic; origin:
         the caller the context was entered with (a registered origin name), context: that context's name (a
-        registered context; "" = the default context, untracked), both kept by the Entry for its exit."""
+        registered context; "" = the default context, untracked), both kept by the Entry for its exit.  parent
+        (tree=True): the Entry this one is nested in (the context's current entry, CtEntry.parent); its resource
+        is what context.getLastNode() answers, None = the context's EntranceNode.  The Entry keeps it."""
+        if parent is not None and not self.tree:
+            raise ValueError("parent needs a LocalSentinel(tree=True)")
+        pa = None
+        if self.tree and context:
+            pa = [parent.rid if parent is not None else SGA_PARENT_ENTRANCE]
         rid = self.ids[resource]
         inbound = entry_type == "IN"
         # the whole argument vector (SGA_EV_ARGS): ParamFlowSlot indexes args by each rule's paramIdx
@@ -422,13 +516,13 @@ class LocalSentinel:
         fl = (EV_PRIORITIZED if prioritized else 0) | EV_ARGS | (EV_INBOUND if inbound else 0)
         dec, wait = self.submit([KIND_ENTRY], [rid], [now], [batch_count], [fl], None, [word], pvals,
                                 origin=[self.origin_id(origin)] if origin else None,
-                                context=[self.context_id(context)] if context else None)
+                                context=[self.context_id(context)] if context else None, parent=pa)
         d = int(dec[0])
         if d in _EXC:
             raise _EXC[d](resource)
         param = param_value(args[0]) if len(args) > 0 and args[0] is not None and \
             not isinstance(args[0], (list, tuple)) else None
-        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin, context)
+        return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin, context, parent)
 
     def node(self, resource, now: int) -> NodeView:
         """ClusterNode views; resource ENTRY_NODE (or TOTAL_IN_RESOURCE_NAME) is Constants.ENTRY_NODE."""
@@ -531,6 +625,41 @@ class LocalSentinel:
         rid = resource if isinstance(resource, int) else self.ids[resource]
         rows = self.query_nodes(_lib.SGA_NODES_CONTEXT, now, [rid])
         return [(self.contexts[int(r["other"]) - 1], self._view_of(r)) for r in rows]
+
+    # ---- the invocation tree (sga_query_tree: one launch, one wave a DefaultNode)
+    def tree_rows(self, now: int) -> np.ndarray:
+        """One TREE_ROW_DTYPE row per DefaultNode, sorted by (context, resource): its view at `now` and its
+        resolved parent -- a resource id of the same context, or SGA_PARENT_ENTRANCE."""
+        if not self.tree:
+            raise ValueError("tree_rows needs a LocalSentinel(tree=True)")
+        cap = min(self._max_pair_nodes[1], len(self.resources) * len(self.contexts))
+        n = C.c_size_t()
+        out = np.zeros(max(1, cap), dtype=TREE_ROW_DTYPE)
+        check(_lib.load().sga_query_tree(self.engine.handle, now, out.ctypes.data, cap, C.byref(n)),
+              self.engine.handle, "treeRows")
+        return out[:n.value]
+
+    def invocation_tree(self, now: int) -> TreeNode:
+        """Constants.ROOT -> the EntranceNodes of the registered contexts that have a DefaultNode, ascending
+        context id -> their DefaultNodes, children in ascending resource id under every node (the reference's
+        child order is a HashSet's: parity-unpinned).  DefaultNode views are the engine's; EntranceNode and ROOT
+        views are entrance_view over their direct children in that order.  The default context appears only if
+        the caller registered its name and submitted its entries with that id (context 0 is untracked), and a
+        context nobody has entered has no EntranceNode here."""
+        rows = self.tree_rows(now)
+        root_children: List[TreeNode] = []
+        for cid in sorted({int(c) for c in rows["context"]}):
+            mine = [r for r in rows if int(r["context"]) == cid]  # ascending resource id
+            made = {int(r["resource"]): TreeNode(self.resources[int(r["resource"])], self._view_of(r), False, [])
+                    for r in mine}
+            top: List[TreeNode] = []
+            for r in mine:
+                p = int(r["parent"])
+                (top if p == SGA_PARENT_ENTRANCE else made[p].children).append(made[int(r["resource"])])
+            root_children.append(TreeNode(self.contexts[cid - 1],
+                                          entrance_view([t.view for t in top], self.statistic_max_rt), True, top))
+        return TreeNode(ROOT_NAME, entrance_view([t.view for t in root_children], self.statistic_max_rt), True,
+                        root_children)
 
     def nodes_device(self, now: int, table: int = 0, not_zero: bool = False, cap: Optional[int] = None, stream=None):
         """Every node of the table into device memory (sga_query_nodes_device), asynchronous on `stream` (a torch
