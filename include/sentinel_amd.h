@@ -441,9 +441,11 @@ int sga_event_post(sga_engine *e, uint8_t kind, uint32_t resource, int64_t ts, i
 #define SGA_BLOCK_DEGRADE 3  /* DegradeException */
 #define SGA_PASS_WAIT 4      /* PriorityWaitException: passed after wait_ms, not counted as pass */
 #define SGA_BLOCK_SYSTEM 5   /* SystemBlockException (SystemSlot, inbound entries only) */
+#define SGA_BLOCK_AUTHORITY 6   /* AuthorityException; wait_ms 0 */
 
 /* event kinds: 0 entry, 1 exit of a passed entry, 2 an entry blocked by a slot outside the engine
- * (AuthoritySlot or a custom slot ahead of the checks): StatisticSlot's BlockException branch only --
+ * (a custom slot ahead of the checks, or an AuthoritySlot the caller keeps -- the engine's own runs through
+ * sga_load_authority_rules): StatisticSlot's BlockException branch only --
  * increaseBlockQps on the node and, inbound, on ENTRY_NODE (StatisticSlot.java:121-135).  Kind 2 events
  * report SGA_PASS and are decided in arrival order by one lane. */
 #define SGA_KIND_ENTRY 0
@@ -785,6 +787,29 @@ typedef struct sga_tree_row {
  * in `out` unsorted.  No contexts registered: SGA_OK, 0 rows.  EntranceNode and Constants.ROOT values are sums
  * over these rows (EntranceNode.java:45-126), formed by the host. */
 int sga_query_tree(sga_engine *e, int64_t now, sga_tree_row *out, size_t cap, size_t *n_out);
+
+/* ---- AuthoritySlot (no struct changes: new entry points only) ---- */
+#define SGA_AUTHORITY_WHITE 0
+#define SGA_AUTHORITY_BLACK 1
+
+/* AuthorityRuleManager.loadAuthorityConf (AuthorityRuleManager.java:110-143) over ids.
+ * n rules in CSR form: rule k is on resource[k] with strategy[k] and the origin ids
+ * origin_ids[list_off[k] .. list_off[k+1]).  Ids are 1..n_origins or SGA_LIMIT_UNKNOWN (dropped); anything
+ * else, a resource >= n_resources, a strategy < 0 or a decreasing list_off: SGA_EINVAL, nothing loaded.
+ * The first rule of a resource wins; n == 0 clears.  Returns the number of rules kept.
+ * A load replaces the whole set and touches no node and no rater.  AuthorityRuleChecker.passCheck
+ * (AuthorityRuleChecker.java:30-66) then runs for every kind 0 event of every entry point that takes an origin
+ * array (host and device, _origin, _ctx and _tree), after the pair nodes' claim and ahead of SystemSlot: origin 0
+ * passes; SGA_AUTHORITY_BLACK blocks an origin in the list, SGA_AUTHORITY_WHITE one that is not; any other strategy
+ * passes.  A blocked entry is counted exactly as a SGA_KIND_BLOCKED event of the caller's (its resource replays in
+ * arrival order that chunk) and answers SGA_BLOCK_AUTHORITY, wait_ms 0.  The caller's kind array is never written.
+ * Entry points without an origin array, the sga_event_* queue and the JNI shim carry origin 0: never blocked. */
+int sga_load_authority_rules(sga_engine *e, const uint32_t *resource, const int32_t *strategy,
+                             const uint32_t *list_off, size_t n, const uint32_t *origin_ids);
+
+/* AuthorityRuleChecker.passCheck for n (resource, origin) pairs in one launch of the same kernel:
+ * pass[i] = 1 / 0.  Touches no state.  Ids out of range: SGA_EINVAL. */
+int sga_authority_check(sga_engine *e, const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass);
 
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {

@@ -26,7 +26,7 @@ from urllib.parse import unquote_plus
 
 from .javautil import double_to_string, is_blank
 from .local import ENTRY_NODE, MetricNode, NodeView, SystemRule
-from .rules import (ClusterFlowConfig, DegradeRule, FlowRule, ParamFlowClusterConfig, ParamFlowItem,
+from .rules import (AuthorityRule, ClusterFlowConfig, DegradeRule, FlowRule, ParamFlowClusterConfig, ParamFlowItem,
                     ParamFlowRule)
 
 SERVER_ERROR_MESSAGE = "Command server error"
@@ -382,8 +382,8 @@ _RULE_TYPES = {"flow": FlowRule, "degrade": DegradeRule, "system": SystemRule}
 
 class CommandCenter:
     """The handlers over one LocalSentinel.  managers: {"flow": FlowRuleManager, "degrade": DegradeRuleManager,
-    "system": SystemRuleManager, "param": ParamFlowRuleManager} (a missing one answers as an empty list and
-    refuses setRules); metric_searcher: the MetricSearcher over the files MetricTimerListener writes; clock: the
+    "system": SystemRuleManager, "param": ParamFlowRuleManager, "authority": AuthorityRuleManager} (a missing one
+    answers as an empty list and refuses setRules); metric_searcher: the MetricSearcher over the files MetricTimerListener writes; clock: the
     engine's `now` in ms (the mocked TimeUtil of the tests, the wall clock by default)."""
 
     def __init__(self, sentinel, managers: Dict[str, object], metric_searcher=None,
@@ -441,8 +441,8 @@ class CommandCenter:
 
     def _get_rules(self, p):
         kind = (p.get("type") or "").lower()
-        if kind == "authority":
-            return "[]"  # AuthoritySlot stays outside the engine
+        if kind == "authority":  # served by an AuthorityRuleManager; without one, as before the engine ran the slot
+            return self._rules_json("authority") if "authority" in self.managers else "[]"
         if kind not in _RULE_TYPES:
             raise ValueError("invalid type")
         return self._rules_json(kind)
@@ -465,6 +465,8 @@ class CommandCenter:
         if data:
             data = unquote_plus(data, encoding="utf-8")  # the handler decodes once more
         if kind == "authority":
+            if "authority" in self.managers:
+                return self._load("authority", AuthorityRule, data)
             raise ValueError("authority rules are not served: the engine does not run AuthoritySlot")
         if kind not in _RULE_TYPES:
             raise ValueError("invalid type")

@@ -2664,6 +2664,21 @@ int sga_context_nodes_of(sga_engine *e, uint32_t resource, uint32_t *contexts, s
     });
 }
 
+int sga_load_authority_rules(sga_engine *e, const uint32_t *resource, const int32_t *strategy,
+                             const uint32_t *list_off, size_t n, const uint32_t *origin_ids) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.load_authority_rules(resource, strategy, list_off, n, origin_ids);
+    });
+}
+
+int sga_authority_check(sga_engine *e, const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.authority_check(resource, origin, n, pass);
+    });
+}
+
 int sga_load_system_rules(sga_engine *e, const sga_system_rule *rules, size_t n) {
     if (n && !rules) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) { return g.flow.load_system_rules(rules, n); });

@@ -1289,6 +1289,51 @@ __global__ __launch_bounds__(kT) void k_lfail(const uint32_t *gate, const uint32
     }
 }
 
+// AuthoritySlot.entry (AuthoritySlot.java:39-68), after ClusterBuilderSlot and ahead of SystemSlot, as a pass over
+// the chunk ahead of every other kernel: one lane an event.  AuthorityRuleChecker.passCheck (:30-66) over ids --
+// the empty origin passes; `contain` is membership of the origin in the rule's sorted slice (a binary search: at
+// most 1 + log2(n) loads whatever the order the names were written in); BLACK blocks a contained origin, WHITE
+// one that is not.  A failing entry becomes SGA_KIND_BLOCKED in the chunk's effective kind, which the claim
+// pass, the CacheMap bookkeeping, the classification, every replay and the statistics passes read in place of
+// the caller's: StatisticSlot's BlockException branch, already exact on every dispatch form, and on the
+// arrival-order lane ahead of the SystemRule check.  kind null (sga_authority_check): every pair is an entry.
+__device__ __forceinline__ bool authority_contains(const uint32_t *__restrict__ ids, uint32_t n, uint32_t o) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ids[mid] < o) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && ids[lo] == o;
+}
+
+__global__ __launch_bounds__(kT) void k_authority(AuthState a, const uint8_t *__restrict__ kind,
+                                                  const uint32_t *__restrict__ resource,
+                                                  const uint32_t *__restrict__ origin, uint32_t n,
+                                                  uint8_t *__restrict__ ekind, uint8_t *__restrict__ turned) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t kd = kind ? kind[i] : (uint8_t)SGA_KIND_ENTRY;
+    const uint32_t r = resource[i], o = origin[i];
+    bool block = false;
+    if (kd == SGA_KIND_ENTRY && r < a.nres && o != 0) {
+        const AuthRuleDev R = a.rule[r];
+        if (R.strategy != kAuthNone)
+            block = authority_contains(a.pool + R.off, R.n, o) == (R.strategy == SGA_AUTHORITY_BLACK);
+    }
+    if (ekind) ekind[i] = block ? (uint8_t)SGA_KIND_BLOCKED : kd;
+    turned[i] = block ? 1 : 0;
+}
+
+// The chunk's last word on the entries k_authority turned: AuthorityException, no wait
+__global__ __launch_bounds__(kT) void k_authority_answer(const uint8_t *__restrict__ turned, uint32_t n,
+                                                         int8_t *decision, int32_t *wait_ms) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n || !turned[i]) return;
+    decision[i] = SGA_BLOCK_AUTHORITY;
+    wait_ms[i] = 0;
+}
+
 __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *__restrict__ kind,
                        const uint32_t *__restrict__ resource, const uint32_t *__restrict__ ts_off, int64_t ts_base,
                        const int32_t *__restrict__ acquire, const uint8_t *__restrict__ flags,
@@ -7578,6 +7623,10 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
             ids[k] = ptab[k].ids.p;
         }
     const bool pairs = origin || context;
+    // AuthoritySlot: a launch of its own ahead of the claim pass (k_lsmall keeps its registers); the kernels
+    // below read the effective kind in device memory, the page-locked copy stays the caller's
+    const uint8_t *const dk_in = dk;
+    dk = authority_pass(dk_in, dres, ids[kPairOrigin], m, stream);
     const uint32_t *dpar_ids = nullptr;  // the enclosing entries, for the DefaultNodes the chunk creates
     if (parent && context) {
         dpar_ids = ptab[kPairContext].parents.p;
@@ -7600,6 +7649,7 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
     SGA_HIP_CHECK(hipGetLastError());
     if (pairs)
         pair_apply(dk, dres, ids, dts, lo, dacq, dfl, drt, (const int8_t *)(d + o_dec), m, nullptr, true, stream);
+    if (dk != dk_in) authority_answer(m, (int8_t *)(d + o_dec), (int32_t *)(d + o_wait), stream);
     if (copy) SGA_HIP_CHECK(hipMemcpyAsync(h + o_dec, d + o_dec, all_bytes - o_dec, hipMemcpyDeviceToHost, stream));
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
     std::memcpy(decision, h + o_dec, m);
@@ -7750,9 +7800,12 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                 SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k] + b, m * 4, hipMemcpyHostToDevice, stream));
         if (parent)
             SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent + b, m * 4, hipMemcpyHostToDevice, stream));
+        // AuthoritySlot: the chunk's effective kind, read below wherever the caller's was
+        const uint8_t *const ek = authority_pass(d_kind.p, d_resid.p, ids[kPairOrigin], (uint32_t)m, stream);
+        const bool auth = ek != d_kind.p;
         // pair nodes exist ahead of every check; a full table refuses the chunk
         if (pairs)
-            if (const int rc = pair_claim(d_kind.p, d_resid.p, ids, (uint32_t)m, nullptr, stream,
+            if (const int rc = pair_claim(ek, d_resid.p, ids, (uint32_t)m, nullptr, stream,
                                           parent ? ptab[kPairContext].parents.p : nullptr))
                 return rc;
         SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, stream));
@@ -7762,20 +7815,21 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, stream));
         // CacheMap capacity: owners that could pass theirs switch to LRU mode (both paths below)
         pair_ctx(ids, stream);
-        lru_prepare(d_kind.p, d_resid.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
+        lru_prepare(ek, d_resid.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
                     any_list ? d_pvals.p : nullptr, (uint32_t)m, stream);
         const FlowState st = state();
         const uint32_t nb = (uint32_t)((m + kT - 1) / kT);
         // kind 2 / 3 events and argument lists stay on the parallel pipeline (their resources replay per resource,
         // F_SPECIAL); SystemRules read ENTRY_NODE across resources: one lane in arrival order
         if (has_in && sys.check) {
-            hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, sys, d_kind.p,
+            hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, sys, ek,
                                d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_param.p, (uint32_t)m, d_dec.p,
                                d_wait.p, has_list ? d_pvals.p : nullptr);
             SGA_HIP_CHECK(hipGetLastError());
             if (pairs)
-                pair_apply(d_kind.p, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
+                pair_apply(ek, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
                            nullptr, false, stream);
+            if (auth) authority_answer((uint32_t)m, d_dec.p, d_wait.p, stream);
             SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
             if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
             uint32_t ovf = 0;
@@ -7790,10 +7844,10 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
             seq += m;
             continue;
         }
-        FlowScratch fsc = special_scratch(sc, d_kind.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
+        FlowScratch fsc = special_scratch(sc, ek, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
                                           has_list ? d_pvals.p : nullptr, d_resid.p);
         const uint64_t *evp = fsc.ev_param;
-        hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, stream, st, fsc, d_kind.p, d_resid.p, d_ts.p, lo, d_acq.p,
+        hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, stream, st, fsc, ek, d_resid.p, d_ts.p, lo, d_acq.p,
                            d_flags.p, param ? d_param.p : nullptr, (uint32_t)m, sc.keys[0], sc.pay[0], d_dec.p, d_wait.p);
         const int np = radix_sort_pairs(sc.keys[0], sc.pay[0], sc.keys[1], sc.pay[1], m, bits, sc.radix, stream);
         const uint32_t *keys = sc.keys[np & 1];
@@ -7836,11 +7890,12 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         hipLaunchKernelGGL(k_lresults, dim3(nb), dim3(kT), 0, stream, st, fsc, pay, d_dec.p, d_wait.p);
         if (has_in)  // ENTRY_NODE statistics of the inbound events
             hipLaunchKernelGGL(k_entry_stats, dim3(1), dim3(kEnTile), 0, stream, st, (int64_t)cfg.statistic_max_rt,
-                               d_kind.p, d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m);
+                               ek, d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m);
         SGA_HIP_CHECK(hipGetLastError());
         if (pairs)  // pair-node statistics from the finished decisions
-            pair_apply(d_kind.p, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
+            pair_apply(ek, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
                        nullptr, false, stream);
+        if (auth) authority_answer((uint32_t)m, d_dec.p, d_wait.p, stream);
         SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
         if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
         uint32_t ovf = 0;
@@ -7931,6 +7986,10 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     const uint32_t gb = std::min<uint32_t>(nb, 1024);
     hipLaunchKernelGGL(k_lgate, dim3(gb), dim3(kT), 0, s, d_kind_in, d_resource, d_acquire, flags_p, param_p, m, nres,
                        (int)sys.check, (uint64_t)(d_param_values ? n_values : 0), d_gate.p, d_param_values);
+    // AuthoritySlot: the chunk's effective kind in the engine's own array (the caller's buffer is only read; the gate
+    // has validated it), read below wherever the caller's was
+    const uint8_t *const d_kind_c = d_kind_in;
+    d_kind_in = authority_pass(d_kind_c, d_resource, d_origin_in, m, s);
     if (pairs)  // pair nodes exist ahead of every check; a full table or a bad id closes the gate
         if (const int rc = pair_claim(d_kind_in, d_resource, ids, m, d_gate.p, s, d_parent_in)) return rc;
     pair_ctx(ids, s);
@@ -7987,6 +8046,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     if (pairs)  // pair-node statistics from the finished decisions (either path's)
         pair_apply(d_kind_in, d_resource, ids, d_ts_off, ts_base, d_acquire, flags_p, rt_p, d_decision, m, d_gate.p,
                    false, s);
+    if (d_kind_in != d_kind_c) authority_answer(m, d_decision, wait_p, s);  // ahead of k_lfail: a refused chunk answers -1
     hipLaunchKernelGGL(k_lfail, dim3(gb), dim3(kT), 0, s, d_gate.p, d_overflow.p, d_gate.p + 1, m, d_decision, wait_p);
     SGA_HIP_CHECK(hipGetLastError());
     seq += n;
@@ -8390,6 +8450,102 @@ int FlowEngine::load_system_rules(const sga_system_rule *r, size_t n) {
         applied += st;
     }
     return applied;
+}
+
+// AuthorityRuleManager.loadAuthorityConf over ids (validated before anything changes): the first rule of a
+// resource is kept, whatever its strategy; only strategies 0 / 1 reach the device, with their ids sorted, distinct
+// and without the names no event can carry.  A reload replaces the whole table and touches no node and no rater.
+int FlowEngine::load_authority_rules(const uint32_t *resource, const int32_t *strategy, const uint32_t *list_off,
+                                     size_t n, const uint32_t *origin_ids) {
+    if (!nres) return SGA_EINVAL;
+    if (n && (!resource || !strategy || !list_off)) return SGA_EINVAL;
+    const uint32_t n_origins = ptab[kPairOrigin].n_ids;
+    for (size_t k = 0; k < n; ++k) {
+        if (resource[k] >= nres || strategy[k] < 0 || list_off[k + 1] < list_off[k]) return SGA_EINVAL;
+        if (list_off[k + 1] > list_off[k] && !origin_ids) return SGA_EINVAL;
+        for (uint32_t j = list_off[k]; j < list_off[k + 1]; ++j)
+            if (origin_ids[j] != SGA_LIMIT_UNKNOWN && (origin_ids[j] == 0 || origin_ids[j] > n_origins)) return SGA_EINVAL;
+    }
+    std::vector<AuthRuleDev> rule(nres, AuthRuleDev{0, 0, kAuthNone, 0});
+    std::vector<uint8_t> seen(nres, 0);
+    std::vector<uint32_t> pool;
+    uint32_t kept = 0, dev = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t r = resource[k];
+        if (seen[r]) continue;  // "Ignoring redundant rule"
+        seen[r] = 1;
+        ++kept;
+        if (strategy[k] != SGA_AUTHORITY_WHITE && strategy[k] != SGA_AUTHORITY_BLACK) continue;  // passCheck passes
+        const size_t off = pool.size();
+        for (uint32_t j = list_off[k]; j < list_off[k + 1]; ++j)
+            if (origin_ids[j] != SGA_LIMIT_UNKNOWN) pool.push_back(origin_ids[j]);
+        std::sort(pool.begin() + off, pool.end());
+        pool.erase(std::unique(pool.begin() + off, pool.end()), pool.end());
+        rule[r] = AuthRuleDev{(uint32_t)off, (uint32_t)(pool.size() - off), strategy[k], 0};
+        ++dev;
+    }
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));  // no chunk in flight reads the old table
+    if (!dev) {
+        d_auth_rule.release();
+        d_auth_pool.release();
+    } else {
+        if (!d_auth_rule.p) d_auth_rule.alloc(nres);
+        if (d_auth_pool.n < std::max<size_t>(pool.size(), 1)) d_auth_pool.alloc(std::max<size_t>(pool.size(), 1));
+        SGA_HIP_CHECK(hipMemcpyAsync(d_auth_rule.p, rule.data(), (size_t)nres * sizeof(AuthRuleDev),
+                                     hipMemcpyHostToDevice, stream));
+        if (!pool.empty())
+            SGA_HIP_CHECK(hipMemcpyAsync(d_auth_pool.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, stream));
+        if (d_ekind.n < cfg.max_batch) d_ekind.alloc(cfg.max_batch);
+        if (d_aturned.n < cfg.max_batch) d_aturned.alloc(cfg.max_batch);
+        SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    auth_dev = dev;
+    auth_kept = kept;
+    return (int)kept;
+}
+
+const uint8_t *FlowEngine::authority_pass(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin,
+                                          uint32_t m, hipStream_t s) {
+    if (!auth_dev || !origin) return kind;
+    hipLaunchKernelGGL(k_authority, dim3((m + kT - 1) / kT), dim3(kT), 0, s, auth_state(), kind, resource, origin, m,
+                       d_ekind.p, d_aturned.p);
+    SGA_HIP_CHECK(hipGetLastError());
+    return d_ekind.p;
+}
+
+void FlowEngine::authority_answer(uint32_t m, int8_t *decision, int32_t *wait_ms, hipStream_t s) {
+    hipLaunchKernelGGL(k_authority_answer, dim3((m + kT - 1) / kT), dim3(kT), 0, s, d_aturned.p, m, decision, wait_ms);
+    SGA_HIP_CHECK(hipGetLastError());
+}
+
+// AuthorityRuleChecker.passCheck for (resource, origin) pairs: k_authority without a kind array or an effective
+// kind to write, in pieces of the batch capacity.  No rule on the device: everything passes, no launch.
+int FlowEngine::authority_check(const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass) {
+    if (!nres) return SGA_EINVAL;
+    if (n && (!resource || !origin || !pass)) return SGA_EINVAL;
+    const uint32_t n_origins = ptab[kPairOrigin].n_ids;
+    for (size_t i = 0; i < n; ++i)
+        if (resource[i] >= nres || origin[i] > n_origins) return SGA_EINVAL;
+    if (!auth_dev) {
+        std::memset(pass, 1, n);
+        return 0;
+    }
+    const size_t cap = cfg.max_batch;
+    for (int k = 0; k < 2; ++k)
+        if (d_auth_q[k].n < cap) d_auth_q[k].alloc(cap);
+    for (size_t b = 0; b < n; b += cap) {
+        const size_t m = std::min(cap, n - b);
+        SGA_HIP_CHECK(hipMemcpyAsync(d_auth_q[0].p, resource + b, m * 4, hipMemcpyHostToDevice, stream));
+        SGA_HIP_CHECK(hipMemcpyAsync(d_auth_q[1].p, origin + b, m * 4, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_authority, dim3((unsigned)((m + kT - 1) / kT)), dim3(kT), 0, stream, auth_state(),
+                           (const uint8_t *)nullptr, d_auth_q[0].p, d_auth_q[1].p, (uint32_t)m, (uint8_t *)nullptr,
+                           d_aturned.p);
+        SGA_HIP_CHECK(hipGetLastError());
+        SGA_HIP_CHECK(hipMemcpyAsync(pass + b, d_aturned.p, m, hipMemcpyDeviceToHost, stream));
+        SGA_HIP_CHECK(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < m; ++i) pass[b + i] ^= 1;  // turned -> pass
+    }
+    return 0;
 }
 
 int FlowEngine::cb_state(uint32_t r, uint32_t k) {

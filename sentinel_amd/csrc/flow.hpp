@@ -181,6 +181,22 @@ struct PairCtx {
     uint64_t seq_base;
 };
 
+// AuthoritySlot (sga_load_authority_rules): per resource the one AuthorityRule the reference keeps
+// (AuthorityRuleManager.java:110-143) -- its strategy (kAuthNone: no rule) and its limitApp names as a slice of one
+// pool of origin ids, sorted and distinct inside a slice, so AuthorityRuleChecker.passCheck's contain test is a
+// binary search whatever the order the names were written in.
+struct AuthRuleDev {
+    uint32_t off, n;     // pool[off .. off + n)
+    int32_t strategy;    // SGA_AUTHORITY_WHITE / SGA_AUTHORITY_BLACK; kAuthNone
+    uint32_t pad;
+};
+constexpr int32_t kAuthNone = -1;
+struct AuthState {
+    const AuthRuleDev *rule;   // per resource
+    const uint32_t *pool;
+    uint32_t nres;
+};
+
 struct FlowState {
     int64_t *node;
     FlowRuleDev *rules;
@@ -485,6 +501,23 @@ struct FlowEngine {
     int cb_state(uint32_t resource, uint32_t k);
     int metrics(int64_t now, sga_metric_node *out, size_t cap, size_t *n);
     int load_system_rules(const sga_system_rule *r, size_t n);
+    // AuthoritySlot.  auth_dev: rules of strategy 0 / 1 on the device (0: no chunk launches anything for the slot);
+    // auth_kept: what loadAuthorityConf keeps (any strategy >= 0, one per resource).  A chunk that carries an origin
+    // array runs k_authority over its events first: d_ekind takes the chunk's effective kind (the caller's, failing
+    // entries turned into SGA_KIND_BLOCKED), which every later step reads in place of the caller's, d_aturned which
+    // events were turned; authority_answer writes their decisions last.
+    DevBuf<AuthRuleDev> d_auth_rule;
+    DevBuf<uint32_t> d_auth_pool, d_auth_q[2];
+    DevBuf<uint8_t> d_ekind, d_aturned;
+    uint32_t auth_dev = 0, auth_kept = 0;
+    AuthState auth_state() const { return AuthState{d_auth_rule.p, d_auth_pool.p, nres}; }
+    int load_authority_rules(const uint32_t *resource, const int32_t *strategy, const uint32_t *list_off, size_t n,
+                             const uint32_t *origin_ids);
+    int authority_check(const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass);
+    // the chunk's effective kind (kind itself when no rule is on the device or the chunk has no origin array)
+    const uint8_t *authority_pass(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin, uint32_t m,
+                                  hipStream_t s);
+    void authority_answer(uint32_t m, int8_t *decision, int32_t *wait_ms, hipStream_t s);
     SysDev sys{0, 0, 0, 0, 1.7976931348623157e308, 1.7976931348623157e308, 1.7976931348623157e308, INT64_MAX,
                INT64_MAX, -1.0, -1.0};
     DevBuf<sga_metric_node> d_metrics;

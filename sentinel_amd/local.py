@@ -8,6 +8,8 @@ Same names and argument meaning as the Java API the engine replaces:
   ParamFlowRuleManager.loadRules  PF/slots/block/flow/param/ParamFlowRuleManager.java:52
   DegradeRuleManager.loadRules    CORE/slots/block/degrade/DegradeRuleManager.java:108
   SystemRuleManager.loadRules     CORE/slots/system/SystemRuleManager.java:114-300 (SystemSlot, inbound only)
+  AuthorityRuleManager.loadRules  CORE/slots/block/authority/AuthorityRuleManager.java:110-164 (AuthoritySlot: entries
+                                  submitted with an origin; AuthorityRuleChecker.passCheck -> authority_check)
   Constants.ENTRY_NODE            CORE/Constants.java:66 -> LocalSentinel.node(ENTRY_NODE), metrics rows
   ClusterNode statistics          CORE/node/StatisticNode.java:185-250 -> LocalSentinel.node
   ContextUtil.enter(name, origin) CORE/context/ContextUtil.java:116-160 -> the `origin` of entry / submit
@@ -38,7 +40,7 @@ import numpy as np
 from . import _lib
 from ._lib import SGA_PARENT_ENTRANCE, SgaConfig, SgaDegradeRule, SgaFlowRule, SgaNodeView, SgaParamRule, check
 from .cluster import Engine  # noqa: F401  (one engine serves both paths)
-from .rules import DegradeRule, FlowRule, ParamFlowRule, RuleConstant  # noqa: F401
+from .rules import AuthorityRule, DegradeRule, FlowRule, ParamFlowRule, RuleConstant  # noqa: F401
 
 
 class Decision:
@@ -48,6 +50,7 @@ class Decision:
     BLOCK_DEGRADE = 3
     PASS_WAIT = 4
     BLOCK_SYSTEM = 5
+    BLOCK_AUTHORITY = 6
 
 
 EV_PRIORITIZED = 1
@@ -85,8 +88,13 @@ class SystemBlockException(BlockException):
     pass
 
 
+class AuthorityException(BlockException):
+    pass
+
+
 _EXC = {Decision.BLOCK_FLOW: FlowException, Decision.BLOCK_PARAM: ParamFlowException,
-        Decision.BLOCK_DEGRADE: DegradeException, Decision.BLOCK_SYSTEM: SystemBlockException}
+        Decision.BLOCK_DEGRADE: DegradeException, Decision.BLOCK_SYSTEM: SystemBlockException,
+        Decision.BLOCK_AUTHORITY: AuthorityException}
 
 
 def param_value(x) -> int:
@@ -709,6 +717,18 @@ class LocalSentinel:
         rid = resource if isinstance(resource, int) else self.ids[resource]
         return _lib.load().sga_circuit_breaker_state(self.engine.handle, rid, k)
 
+    def authority_check(self, resources, origins) -> np.ndarray:
+        """AuthorityRuleChecker.passCheck of the loaded AuthorityRules for (resource id, origin id) pairs, in one
+        launch of the kernel the slot runs (sga_authority_check): a bool array, True = passes.  Touches no state."""
+        r = np.ascontiguousarray(resources, dtype=np.uint32)
+        o = np.ascontiguousarray(origins, dtype=np.uint32)
+        if len(r) != len(o):
+            raise ValueError("resources and origins differ in length")
+        out = np.zeros(max(1, len(r)), dtype=np.uint8)
+        check(_lib.load().sga_authority_check(self.engine.handle, r.ctypes.data, o.ctypes.data, len(r),
+                                              out.ctypes.data), self.engine.handle, "authorityCheck")
+        return out[:len(r)].astype(bool)
+
 
 class ClusterStateManager:
     """ClusterStateManager (CORE/cluster/ClusterStateManager.java) as the local path sees it:
@@ -871,6 +891,57 @@ class DegradeRuleManager:
             a.stat_interval_ms = r.stat_interval_ms
         return check(_lib.load().sga_load_degrade_rules(self.s.engine.handle, arr, len(rules)), self.s.engine.handle,
                      "DegradeRuleManager.loadRules")
+
+
+class AuthorityRuleManager:
+    """AuthorityRuleManager.loadRules (CORE/slots/block/authority/AuthorityRuleManager.java:110-164): one rule per
+    resource, the first valid one in list order.  The engine's AuthoritySlot then checks every entry submitted with
+    an origin (sga_load_authority_rules); a blocked entry answers Decision.BLOCK_AUTHORITY."""
+
+    def __init__(self, sentinel: LocalSentinel):
+        self.s = sentinel
+        self._kept: List[AuthorityRule] = []
+
+    @staticmethod
+    def is_valid_rule(rule: Optional[AuthorityRule]) -> bool:
+        """AuthorityRuleManager.isValidRule: resource and limitApp not blank, strategy >= 0."""
+        return (rule is not None and bool(rule.resource) and bool(rule.resource.strip()) and rule.strategy >= 0 and
+                bool(rule.limit_app) and bool(rule.limit_app.strip()))
+
+    def get_rules(self) -> list:
+        """The rules kept by the last load, in load order (the reference's getRules() walks a map); a rule naming
+        a resource this sentinel does not have stays in it and applies to nothing."""
+        return list(self._kept)
+
+    def load_rules(self, rules: List[AuthorityRule]) -> int:
+        """Replaces the whole set (an empty list clears it); returns the number of rules kept.  Each rule's
+        limitApp.split(",") is resolved to origin ids name by name, exactly (no trimming: AuthorityRuleChecker
+        compares with equals); a name that is no registered origin is sent as SGA_LIMIT_UNKNOWN, which the engine
+        drops, since no event can carry it."""
+        kept: List[AuthorityRule] = []
+        seen = set()
+        for r in rules or []:
+            if not self.is_valid_rule(r) or r.resource in seen:
+                continue
+            seen.add(r.resource)
+            kept.append(r)
+        send = [r for r in kept if r.resource in self.s.ids]
+        oids = self.s.origin_ids
+        res = np.zeros(max(1, len(send)), dtype=np.uint32)
+        strat = np.zeros(max(1, len(send)), dtype=np.int32)
+        off = np.zeros(len(send) + 1, dtype=np.uint32)
+        ids: List[int] = []
+        for i, r in enumerate(send):
+            res[i] = self.s.ids[r.resource]
+            strat[i] = r.strategy
+            ids.extend(oids.get(name, _lib.SGA_LIMIT_UNKNOWN) for name in r.limit_app.split(","))
+            off[i + 1] = len(ids)
+        idv = np.asarray(ids if ids else [0], dtype=np.uint32)
+        check(_lib.load().sga_load_authority_rules(self.s.engine.handle, res.ctypes.data, strat.ctypes.data,
+                                                   off.ctypes.data, len(send), idv.ctypes.data),
+              self.s.engine.handle, "AuthorityRuleManager.loadRules")
+        self._kept = kept
+        return len(kept)
 
 
 @dataclass

@@ -4,6 +4,7 @@
   ParamFlowRule    PF/slots/block/flow/param/ParamFlowRule.java:45-83, ParamFlowItem.java:28-40,
                    ParamFlowClusterConfig.java:32-44
   DegradeRule      CORE/slots/block/degrade/DegradeRule.java:59-84
+  AuthorityRule    CORE/slots/block/authority/AuthorityRule.java
   RuleConstant     CORE/slots/block/RuleConstant.java:24-61
 """
 from dataclasses import dataclass, field
@@ -27,6 +28,8 @@ class RuleConstant:
     CONTROL_BEHAVIOR_WARM_UP_RATE_LIMITER = 3
     LIMIT_APP_DEFAULT = "default"
     LIMIT_APP_OTHER = "other"
+    AUTHORITY_WHITE = 0
+    AUTHORITY_BLACK = 1
 
 
 class ClusterRuleConstant:
@@ -93,6 +96,14 @@ class ParamFlowRule:
     param_flow_item_list: List[ParamFlowItem] = field(default_factory=list)
     cluster_mode: bool = False
     cluster_config: Optional[ParamFlowClusterConfig] = None
+
+
+@dataclass
+class AuthorityRule:
+    """CORE/slots/block/authority/AuthorityRule.java: limit_app is the comma-separated list of origin names."""
+    resource: str = ""
+    limit_app: str = ""
+    strategy: int = RuleConstant.AUTHORITY_WHITE
 
 
 @dataclass
