@@ -2430,6 +2430,28 @@ static int cluster_param_plumb(Engine &g) {
     return SGA_OK;
 }
 
+// Before a local batch of either entry: the ClusterStateManager mode, the cluster parameter state, and every
+// cluster-mode FlowRule's token server slot.
+static int cluster_prepare(Engine &g) {
+    g.flow.cluster_on = g.cluster_server == 1 ? 1 : 0;
+    if (const int rc = cluster_param_plumb(g); rc != SGA_OK) return rc;
+    if (!g.flow.has_cluster_rules) return SGA_OK;
+    g.flow.cluster_st = g.state();
+    const int rc = g.flow.resolve_cluster(
+        [&](int64_t fid) -> int32_t {
+            auto it = g.slot_of.find(fid);
+            if (it == g.slot_of.end()) return -1;
+            const SlotHost &h = g.slots[it->second];
+            if (!h.active) return -1;
+            if (h.ns >= 0 && g.nss[h.ns].has_limit) return -2;
+            return (int32_t)it->second;
+        },
+        g.cluster_gen);
+    if (rc != SGA_OK)
+        g.err = "cluster-mode flow rule: flowId shared by two resources or namespace with a request limiter";
+    return rc;
+}
+
 int sga_submit_events(sga_engine *e, const uint8_t *kind, const uint32_t *resource, const int64_t *ts,
                       const int32_t *acquire, const uint8_t *flags, const int64_t *rt, const uint64_t *param,
                       size_t n, int8_t *decision, int32_t *wait_ms) {
@@ -2467,25 +2489,7 @@ int sga_submit_events_tree(sga_engine *e, const uint8_t *kind, const uint32_t *r
     if (n && (!kind || !resource || !ts || !acquire || !decision)) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
-        g.flow.cluster_on = g.cluster_server == 1 ? 1 : 0;
-        if (const int rc = cluster_param_plumb(g); rc != SGA_OK) return rc;
-        if (g.flow.has_cluster_rules) {
-            g.flow.cluster_st = g.state();
-            const int rc = g.flow.resolve_cluster(
-                [&](int64_t fid) -> int32_t {
-                    auto it = g.slot_of.find(fid);
-                    if (it == g.slot_of.end()) return -1;
-                    const SlotHost &h = g.slots[it->second];
-                    if (!h.active) return -1;
-                    if (h.ns >= 0 && g.nss[h.ns].has_limit) return -2;
-                    return (int32_t)it->second;
-                },
-                g.cluster_gen);
-            if (rc != SGA_OK) {
-                g.err = "cluster-mode flow rule: flowId shared by two resources or namespace with a request limiter";
-                return rc;
-            }
-        }
+        if (const int rc = cluster_prepare(g); rc != SGA_OK) return rc;
         return g.flow.submit(kind, resource, ts, acquire, flags, rt, param, n, decision, wait_ms, param_values,
                              n_values, origin, context, parent);
     });
@@ -2531,25 +2535,7 @@ int sga_submit_events_tree_device(sga_engine *e, const uint8_t *d_kind, const ui
     return guarded(e, [&](Engine &g) {
         if (n > g.cfg.max_batch) return SGA_ERANGE;
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
-        g.flow.cluster_on = g.cluster_server == 1 ? 1 : 0;
-        if (const int rc = cluster_param_plumb(g); rc != SGA_OK) return rc;
-        if (g.flow.has_cluster_rules) {
-            g.flow.cluster_st = g.state();
-            const int rc = g.flow.resolve_cluster(
-                [&](int64_t fid) -> int32_t {
-                    auto it = g.slot_of.find(fid);
-                    if (it == g.slot_of.end()) return -1;
-                    const SlotHost &h = g.slots[it->second];
-                    if (!h.active) return -1;
-                    if (h.ns >= 0 && g.nss[h.ns].has_limit) return -2;
-                    return (int32_t)it->second;
-                },
-                g.cluster_gen);
-            if (rc != SGA_OK) {
-                g.err = "cluster-mode flow rule: flowId shared by two resources or namespace with a request limiter";
-                return rc;
-            }
-        }
+        if (const int rc = cluster_prepare(g); rc != SGA_OK) return rc;
         // buffers grow on the engine stream before a caller stream is ordered after it
         if (const int rc = g.flow.ensure_scratch()) return rc;
         if (const int rc = g.flow.ensure_maps(n + n_values)) return rc;

@@ -1227,7 +1227,7 @@ __device__ __forceinline__ void entry_node_after_exit(const Ctx &c, int64_t t, i
 // System-rule mode: the whole batch by one lane in arrival order (checkSystem reads ENTRY_NODE,
 // which every earlier inbound decision of every resource changed).
 // Device entry gate (FlowEngine::submit_device): k_lgate sets kGateSeq when the chunk must be replayed
-// in arrival order (inbound events under a SystemRule, or Collection arguments), kGateIn when it holds
+// in arrival order (inbound events under a SystemRule check), kGateIn when it holds
 // inbound events, kGateBad on invalid input (the chunk is not applied).  A null gate (host entry)
 // lets every kernel run; the host launches only the ones the chunk needs.
 constexpr uint32_t kGateSeq = 1, kGateIn = 2, kGateBad = 4;
@@ -6664,16 +6664,17 @@ void FlowEngine::lru_sync_rules() {
     SGA_HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-void FlowEngine::lru_prepare(const uint8_t *kind, const uint32_t *resource, const uint8_t *flags, const uint64_t *param,
-                             const uint64_t *pvals, uint32_t n, hipStream_t s) {
-    if (!d_psize.p || h_prules.empty()) return;
+void FlowEngine::lru_prepare(const Chunk &c) {
+    if (!lru_counts()) return;
+    const uint32_t n = c.m;
+    hipStream_t s = c.s;
     if (d_lneed.n < n) d_lneed.grow(n, s);
     const FlowState st = state();
     const uint32_t nb = std::min<uint32_t>((n + kT - 1) / kT, 2048);
     hipLaunchKernelGGL(k_lru_claim, dim3(std::max<uint32_t>((n + kLruChunk - 1) / kLruChunk, 1)), dim3(kT), 0, s, st,
-                       kind, resource, flags, param, pvals, n);
-    hipLaunchKernelGGL(k_lru_count, dim3(std::max<uint32_t>(nb, 1)), dim3(kT), 0, s, st, kind, resource, flags,
-                       param, pvals);
+                       c.kind, c.resource, c.flags, c.param, c.pvals, n);
+    hipLaunchKernelGGL(k_lru_count, dim3(std::max<uint32_t>(nb, 1)), dim3(kT), 0, s, st, c.kind, c.resource, c.flags,
+                       c.param, c.pvals);
     const uint32_t no = st.nprid + st.ntslot;
     hipLaunchKernelGGL(k_lru_decide, dim3((no + kT - 1) / kT), dim3(kT), 0, s, st);
     hipLaunchKernelGGL(k_lru_collect, dim3(2048), dim3(kT), 0, s, st);
@@ -7321,12 +7322,6 @@ int FlowEngine::ensure_maps(size_t m) {
     return 0;
 }
 
-// SGA_NO_PSEG=1 (A/B knob): parameter-only resources keep the event-by-event replay
-static bool pseg_on() {
-    static const bool off = getenv("SGA_NO_PSEG") && atoi(getenv("SGA_NO_PSEG")) == 1;
-    return !off;
-}
-
 #ifdef SGA_TEST_HOOKS
 // The test-only build's record of the last host chunk (FlowEngine::submit): which scratch its dispatch counts
 // are in, and what the host code decided about it.  Read back by sga_test_local_dispatch.
@@ -7339,10 +7334,22 @@ struct HookChunk {
 static HookChunk g_hook_chunk;
 #endif
 
-void FlowEngine::launch_pseg(const FlowState &st, const FlowScratch &g, const Payload *pay, const uint32_t *keys,
-                             int64_t ts_base, const int64_t *rt, const uint64_t *param, int8_t *decision,
-                             int32_t *wait_ms, uint32_t m, hipStream_t s) {
+// the bits of a radix sort whose keys run from 0 to n
+static int key_bits(uint64_t n) {
+    int bits = 1;
+    while (((uint64_t)1 << bits) < n + 1) ++bits;
+    return bits;
+}
+
+void FlowEngine::launch_pseg(const Chunk &c, const FlowState &st, const FlowScratch &g, const Payload *pay,
+                             const uint32_t *keys) {
+    const uint32_t m = c.m;
     if (!g.pseg || m == 0) return;
+    const int64_t ts_base = c.ts_base, *rt = c.rt;
+    const uint64_t *param = g.ev_param;  // what the parallel kernels read as the event's parameter
+    int8_t *decision = c.decision;
+    int32_t *wait_ms = c.wait_ms;
+    hipStream_t s = c.s;
 #ifdef SGA_TEST_HOOKS
     g_hook_chunk.tiled = !h_cbs.empty() && m >= kCbTileMin;
 #endif
@@ -7570,14 +7577,51 @@ int FlowEngine::ensure_scratch() {
     return 0;
 }
 
+// The start of a chunk on every entry, whichever lane decides it afterwards.  A refused pair claim (host entries:
+// a full table) is returned; the device entry's closes the gate instead.
+int FlowEngine::chunk_prologue(Chunk &c, bool small) {
+    authority_pass(c);  // AuthoritySlot: every later step reads c.kind wherever the caller's kind was
+    if (c.pairs())      // pair nodes exist ahead of every check
+        if (const int rc = pair_claim(c)) return rc;
+    // per chunk: a probe sequence that overflowed in an earlier (failed) batch must not fail every later one.  A
+    // failed batch has been partly applied (its node and breaker updates stay); the call reports -ENOMEM.  A small
+    // chunk keeps no dispatch counts, and k_lsmall zeroes the overflow word itself when no count pass can flag it.
+    if (!small) SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, c.s));
+    if (!small || lru_counts()) SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, c.s));
+    pair_ctx(c);
+    lru_prepare(c);  // CacheMap capacity: owners that could pass theirs switch to LRU mode
+    return 0;
+}
+
+// The arrival-order lane: SystemRules read ENTRY_NODE across resources, so one lane replays the chunk.  The host
+// entry chooses it for a chunk with inbound events under a SystemRule check; on the device entry the gate does.
+void FlowEngine::chunk_seq(const Chunk &c) {
+    FlowState st = state();
+    st.gate = c.gate;
+    hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, c.s, st, (int64_t)cfg.statistic_max_rt, sys, c.kind, c.resource,
+                       c.ts_off, c.ts_base, c.acquire, c.flags, c.rt, c.param, c.m, c.decision, c.wait_ms, c.pvals);
+    SGA_HIP_CHECK(hipGetLastError());
+}
+
+// The end of a chunk's device work on every entry: pair-node statistics from the finished decisions, then the
+// answers of the entries AuthoritySlot turned (ahead of the device entry's k_lfail: a refused chunk answers -1).
+void FlowEngine::chunk_epilogue(const Chunk &c, bool seq_lane) {
+    if (c.pairs()) pair_apply(c, seq_lane);
+    if (c.turned()) authority_answer(c);
+}
+
+// The host entries' reading of a chunk's overflow word, after their wait
+int FlowEngine::host_result(uint32_t ovf) {
+    if (ovf & kOvfMissingEntry) throw HipError(kMissingEntryText, __FILE__, __LINE__);  // SGA_EIO
+    return ovf ? SGA_ENOMEM : 0;  // parameter maps full: the chunk is partly applied
+}
+
 // One small chunk (FlowEngine::kSmallEvents): the events and their argument words packed into page-locked memory,
-// one copy to the device, the CacheMap bookkeeping (lru_prepare), k_lsmall, one copy back of the decisions,
-// waits and the overflow word.
-int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire,
+// which the kernels read in place and write the results into (it is mapped into the device's address space,
+// coherent): no copy operation either way, one launch (plus the CacheMap bookkeeping when parameter rules exist).
+int FlowEngine::submit_small(Chunk c, const uint8_t *kind, const uint32_t *resource, const int32_t *acquire,
                              const uint8_t *flags, const int64_t *rt, const uint64_t *param, const uint32_t *ts_off,
-                             int64_t lo, uint32_t m, int8_t *decision, int32_t *wait_ms, const uint64_t *pvals,
-                             size_t npvals, const uint32_t *origin, const uint32_t *context,
-                             const uint32_t *parent) {
+                             int8_t *decision, int32_t *wait_ms, const uint64_t *pvals, size_t npvals) {
     auto a8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
     const size_t o_kind = 0, o_flags = a8(o_kind + kSmallEvents), o_res = a8(o_flags + kSmallEvents),
                  o_ts = o_res + 4 * kSmallEvents, o_acq = o_ts + 4 * kSmallEvents, o_rt = o_acq + 4 * kSmallEvents,
@@ -7586,86 +7630,52 @@ int FlowEngine::submit_small(const uint8_t *kind, const uint32_t *resource, cons
     const size_t o_dec = in_bytes, o_wait = a8(o_dec + kSmallEvents), o_ovf = o_wait + 4 * kSmallEvents,
                  all_bytes = o_ovf + 8;
     if (!h_small.p) h_small.alloc(all_bytes);
-    if (!d_small.p) d_small.alloc(all_bytes);
-    uint8_t *h = h_small.p, *d = d_small.p;
+    uint8_t *h = h_small.p;
+    const size_t m = c.m;
     std::memcpy(h + o_kind, kind, m);
     if (flags) std::memcpy(h + o_flags, flags, m);
     else std::memset(h + o_flags, 0, m);
-    std::memcpy(h + o_res, resource, 4 * (size_t)m);
-    std::memcpy(h + o_ts, ts_off, 4 * (size_t)m);
-    std::memcpy(h + o_acq, acquire, 4 * (size_t)m);
-    if (rt) std::memcpy(h + o_rt, rt, 8 * (size_t)m);
-    else std::memset(h + o_rt, 0, 8 * (size_t)m);
-    if (param) std::memcpy(h + o_param, param, 8 * (size_t)m);
-    else std::memset(h + o_param, 0, 8 * (size_t)m);
+    std::memcpy(h + o_res, resource, 4 * m);
+    std::memcpy(h + o_ts, ts_off, 4 * m);
+    std::memcpy(h + o_acq, acquire, 4 * m);
+    if (rt) std::memcpy(h + o_rt, rt, 8 * m);
+    else std::memset(h + o_rt, 0, 8 * m);
+    if (param) std::memcpy(h + o_param, param, 8 * m);
+    else std::memset(h + o_param, 0, 8 * m);
     if (npvals) std::memcpy(h + o_vals, pvals, 8 * npvals);
-    // The kernels read the page-locked buffer in place and write the results into it (it is mapped into the
-    // device's address space, coherent): no copy operation either way, one launch (plus the CacheMap
-    // bookkeeping when parameter rules exist).  SGA_SMALL_COPY=1 (A/B knob) copies to HBM first.
-    static const bool copy = getenv("SGA_SMALL_COPY") && atoi(getenv("SGA_SMALL_COPY")) == 1;
-    if (copy) {
-        const size_t up = npvals ? o_vals + 8 * npvals : o_vals;  // the argument words end the input region
-        SGA_HIP_CHECK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, stream));
-    } else {
-        d = h;
-    }
-    const bool maps = d_psize.p && !h_prules.empty();  // lru_prepare runs (and may flag the overflow word)
-    if (maps) SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, stream));
-    const uint8_t *dk = d + o_kind, *dfl = d + o_flags;
-    const uint32_t *dres = (const uint32_t *)(d + o_res), *dts = (const uint32_t *)(d + o_ts);
-    const int32_t *dacq = (const int32_t *)(d + o_acq);
-    const int64_t *drt = (const int64_t *)(d + o_rt);
-    const uint64_t *dpar = (const uint64_t *)(d + o_param), *dvals = npvals ? (const uint64_t *)(d + o_vals) : nullptr;
-    const uint32_t *hids[kPairKinds] = {origin, context}, *ids[kPairKinds] = {nullptr, nullptr};
-    for (int k = 0; k < kPairKinds; ++k)
-        if (hids[k]) {
-            SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k], 4 * (size_t)m, hipMemcpyHostToDevice, stream));
-            ids[k] = ptab[k].ids.p;
-        }
-    const bool pairs = origin || context;
-    // AuthoritySlot: a launch of its own ahead of the claim pass (k_lsmall keeps its registers); the kernels
-    // below read the effective kind in device memory, the page-locked copy stays the caller's
-    const uint8_t *const dk_in = dk;
-    dk = authority_pass(dk_in, dres, ids[kPairOrigin], m, stream);
-    const uint32_t *dpar_ids = nullptr;  // the enclosing entries, for the DefaultNodes the chunk creates
-    if (parent && context) {
-        dpar_ids = ptab[kPairContext].parents.p;
-        SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent, 4 * (size_t)m, hipMemcpyHostToDevice, stream));
-    }
-    // pair nodes exist ahead of every check; a full table refuses the chunk
-    if (pairs)
-        if (const int rc = pair_claim(dk, dres, ids, m, nullptr, stream, dpar_ids)) return rc;
-    pair_ctx(ids, stream);
-    lru_prepare(dk, dres, dfl, dpar, dvals, m, stream);  // CacheMap capacity
+    c.kind_in = h + o_kind;  // the page-locked kind stays the caller's: an effective kind is in device memory
+    c.flags = h + o_flags;
+    c.resource = (const uint32_t *)(h + o_res);
+    c.ts_off = (const uint32_t *)(h + o_ts);
+    c.acquire = (const int32_t *)(h + o_acq);
+    c.rt = (const int64_t *)(h + o_rt);
+    c.param = (const uint64_t *)(h + o_param);
+    c.pvals = npvals ? (const uint64_t *)(h + o_vals) : nullptr;
+    c.decision = (int8_t *)(h + o_dec);
+    c.wait_ms = (int32_t *)(h + o_wait);
+    if (const int rc = chunk_prologue(c, true)) return rc;
     FlowScratch fs = sc;
-    fs.in_kind = dk;
-    fs.in_flags = dfl;
-    fs.in_param = dpar;
-    fs.pvals = dvals;
-    fs.in_resource = dres;
-    hipLaunchKernelGGL(k_lsmall, dim3(1), dim3(kLSmall), 0, stream, state(), (int64_t)cfg.statistic_max_rt, fs, dres,
-                       dts, lo, dacq, drt, m, (int8_t *)(d + o_dec), (int32_t *)(d + o_wait), (uint32_t *)(d + o_ovf),
-                       maps ? 0 : 1);
+    fs.in_kind = c.kind;
+    fs.in_flags = c.flags;
+    fs.in_param = c.param;
+    fs.pvals = c.pvals;
+    fs.in_resource = c.resource;
+    hipLaunchKernelGGL(k_lsmall, dim3(1), dim3(kLSmall), 0, c.s, state(), (int64_t)cfg.statistic_max_rt, fs, c.resource,
+                       c.ts_off, c.ts_base, c.acquire, c.rt, c.m, c.decision, c.wait_ms, (uint32_t *)(h + o_ovf),
+                       lru_counts() ? 0 : 1);
     SGA_HIP_CHECK(hipGetLastError());
-    if (pairs)
-        pair_apply(dk, dres, ids, dts, lo, dacq, dfl, drt, (const int8_t *)(d + o_dec), m, nullptr, true, stream);
-    if (dk != dk_in) authority_answer(m, (int8_t *)(d + o_dec), (int32_t *)(d + o_wait), stream);
-    if (copy) SGA_HIP_CHECK(hipMemcpyAsync(h + o_dec, d + o_dec, all_bytes - o_dec, hipMemcpyDeviceToHost, stream));
-    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    chunk_epilogue(c, true);
+    SGA_HIP_CHECK(hipStreamSynchronize(c.s));
     std::memcpy(decision, h + o_dec, m);
-    if (wait_ms) std::memcpy(wait_ms, h + o_wait, 4 * (size_t)m);
+    if (wait_ms) std::memcpy(wait_ms, h + o_wait, 4 * m);
     uint32_t ovf;
     std::memcpy(&ovf, h + o_ovf, 4);
-    if (ovf & kOvfMissingEntry) throw HipError(kMissingEntryText, __FILE__, __LINE__);  // SGA_EIO
-    if (ovf) return SGA_ENOMEM;  // parameter maps full
-    return 0;
+    return host_result(ovf);
 }
 
 // The chunk's view of the scratch for F_SPECIAL events: a new epoch marks their resources (res_special), the
 // original kind / flags / parameters / value lists are what the per-resource replay reads for them.
-FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
-                                        const uint64_t *d_param_in, const uint64_t *d_pvals,
-                                        const uint32_t *d_resource_in) {
+FlowScratch FlowEngine::special_scratch(const Chunk &c) {
     if (d_res_special.n < (size_t)nres + 1) {
         d_res_special.alloc((size_t)nres + 1);
         SGA_HIP_CHECK(hipMemset(d_res_special.p, 0, d_res_special.bytes()));
@@ -7675,15 +7685,68 @@ FlowScratch FlowEngine::special_scratch(const FlowScratch &base, const uint8_t *
         SGA_HIP_CHECK(hipMemsetAsync(d_res_special.p, 0, d_res_special.bytes(), stream));
         epoch = 1;
     }
-    FlowScratch f = base;
+    FlowScratch f = sc;
     f.res_special = d_res_special.p;
     f.epoch = epoch;
-    f.in_kind = d_kind_in;
-    f.in_flags = d_flags_in;
-    f.in_param = d_param_in;
-    f.pvals = d_pvals;
-    f.in_resource = d_resource_in;
+    f.in_kind = c.kind;
+    f.in_flags = c.flags;
+    f.in_param = c.param;
+    f.pvals = c.pvals;
+    f.in_resource = c.resource;
     return f;
+}
+
+// The parallel pipeline.  Kind 2 / 3 events and argument lists stay on it (their resources replay per resource,
+// F_SPECIAL).  With a gate (device entry) every kernel checks it, k_entry_stats is always launched, and k_lseq
+// follows for the gate to choose between the two; without one, k_entry_stats runs only for inbound events.
+void FlowEngine::chunk_pipeline(const Chunk &c, bool inbound) {
+    const uint32_t m = c.m;
+    hipStream_t s = c.s;
+    const int64_t max_rt = (int64_t)cfg.statistic_max_rt, lo = c.ts_base;
+    FlowState st = state();
+    st.gate = c.gate;
+    FlowScratch f = special_scratch(c);
+    f.gate = c.gate;
+    // the flows per (rule, value) segment and the breaker flows: only k_lflows and launch_pseg read the list
+    if (h_prules.empty() && h_cbs.empty()) f.pseg = nullptr;
+    const uint64_t *evp = f.ev_param;  // what the parallel kernels read as the event's parameter
+    const uint32_t nb = (m + kT - 1) / kT;
+    hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, s, st, f, c.kind, c.resource, c.ts_off, lo, c.acquire,
+                       c.flags, c.param, m, f.keys[0], f.pay[0], c.decision, c.wait_ms);
+    const int np = radix_sort_pairs(f.keys[0], f.pay[0], f.keys[1], f.pay[1], m, key_bits(nres), f.radix, s);
+    const uint32_t *keys = f.keys[np & 1];
+    const Payload *pay = f.pay[np & 1];
+    const uint32_t ntiles = (m + kTileElems - 1) / kTileElems;
+    hipLaunchKernelGGL(k_lruns_up, dim3(ntiles), dim3(kT), 0, s, keys, pay, m, nres, (LAgg *)f.tile_agg, f.tile_valid);
+    hipLaunchKernelGGL(k_lruns_tiles, dim3(1), dim3(kT), 0, s, (const LAgg *)f.tile_agg, f.tile_valid, ntiles,
+                       (LAgg *)f.tile_carry, f.counters);
+    hipLaunchKernelGGL(k_lruns_down, dim3(ntiles), dim3(kT), 0, s, keys, pay, c.rt, nres, (const LAgg *)f.tile_carry, f);
+    hipLaunchKernelGGL(k_lexits, dim3(ntiles), dim3(kT), 0, s, pay, c.rt, f);
+    const uint32_t fthreads = std::min<uint32_t>(m, nres);
+    hipLaunchKernelGGL(k_lflows, dim3((fthreads + kT - 1) / kT), dim3(kT), 0, s, st, max_rt, f, pay, keys, lo, c.rt, evp,
+                       c.decision, c.wait_ms);
+    if (has_groups)  // the RELATE groups k_lflows left to a wave each (known from the rule load)
+        hipLaunchKernelGGL(k_lgroup, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, m / kGroupEvents))), dim3(64), 0,
+                           s, st, max_rt, f, pay, lo, c.rt, c.decision, c.wait_ms);
+    launch_pseg(c, st, f, pay, keys);
+    if (st.lru_res) {
+        hipLaunchKernelGGL(k_llru, dim3(64), dim3(64), 0, s, st, max_rt, f, pay, lo, c.rt, evp, c.decision, c.wait_ms);
+        hipLaunchKernelGGL(k_llru_ps, dim3(256), dim3(128), 0, s, st, max_rt, f, pay, lo, evp, c.decision, c.wait_ms);
+    }
+    hipLaunchKernelGGL(k_lwsum, dim3((m / 64 + 3) / 4 + 1), dim3(256), 0, s, st, f, pay);
+    for (int rl = 0; rl < 2; ++rl)
+        hipLaunchKernelGGL(rl ? k_lwave<1> : k_lwave<0>, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, m / 4096))),
+                           dim3(64), 0, s, st, max_rt, f, pay, lo, c.rt, evp, c.decision, c.wait_ms, lwave_prof());
+    print_lwave_prof(s);
+    hipLaunchKernelGGL(k_lheavy, dim3(std::max<uint32_t>(1, std::min<uint32_t>(1024, m / kHeavyEvents))), dim3(64), 0, s,
+                       st, max_rt, f, pay, lo, c.rt, evp, c.decision, c.wait_ms, heavy_prof());
+    if (heavy_prof()) print_heavy_prof();
+    hipLaunchKernelGGL(k_lresults, dim3(nb), dim3(kT), 0, s, st, f, pay, c.decision, c.wait_ms);
+    if (c.gate || inbound)  // ENTRY_NODE statistics of the inbound events
+        hipLaunchKernelGGL(k_entry_stats, dim3(1), dim3(kEnTile), 0, s, st, max_rt, c.kind, c.resource, c.ts_off, lo,
+                           c.acquire, c.flags, c.rt, c.decision, m);
+    SGA_HIP_CHECK(hipGetLastError());
+    if (c.gate) chunk_seq(c);  // acts only when the gate says so
 }
 
 int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int64_t *ts, const int32_t *acquire,
@@ -7693,23 +7756,20 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
     if (!nres) return SGA_EINVAL;
     if (n == 0) return 0;
     if (!context) parent = nullptr;  // only an event with a context creates a DefaultNode
-    const uint32_t *hids[kPairKinds] = {origin, context}, *ids[kPairKinds] = {nullptr, nullptr};
+    const uint32_t *hids[kPairKinds] = {origin, context};
     for (int k = 0; k < kPairKinds; ++k) {
         if (!hids[k]) continue;  // an id past the registered ones refuses the call
         if (!ptab[k].n_ids) return SGA_EINVAL;
         for (size_t i = 0; i < n; ++i)
             if (hids[k][i] > ptab[k].n_ids) return SGA_EINVAL;
-        ids[k] = ptab[k].ids.p;
     }
     // a parent that names no resource, on an event that may create a DefaultNode, refuses the call like a bad id
     for (size_t i = 0; parent && i < n; ++i)
         if (parent[i] >= nres && parent[i] != SGA_PARENT_ENTRANCE && context[i] && resource[i] < nres &&
             kind[i] != SGA_KIND_EXIT)
             return SGA_EINVAL;
-    const bool pairs = origin || context;
-    // Collection / array arguments (SGA_EV_PARAM_LIST): the value array goes to the device once;
-    // chunks holding such events are replayed in arrival order by one lane (k_lseq)
-    // and whole argument vectors (SGA_EV_ARGS: word pairs, lists inside param_values)
+    // Collection / array arguments (SGA_EV_PARAM_LIST) and whole argument vectors (SGA_EV_ARGS: word pairs, lists
+    // inside param_values): the value array goes to the device once
     auto is_list = [&](size_t i) {
         return (flags[i] & SGA_EV_ARGS) ||
                (flags[i] & (SGA_EV_PARAM_LIST | SGA_EV_HAS_PARAM)) == (SGA_EV_PARAM_LIST | SGA_EV_HAS_PARAM);
@@ -7736,10 +7796,7 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
     }
     const size_t cap = cfg.max_batch;
     if (const int rc = ensure_scratch()) return rc;
-    int bits = 1;
-    while (((uint64_t)1 << bits) < (uint64_t)nres + 1) ++bits;
     std::vector<uint32_t> off;
-    std::vector<int64_t> zero_rt;
     for (size_t b = 0; b < n;) {
         size_t m = std::min(cap, n - b);
         int64_t lo = ts[b], hi = ts[b];
@@ -7762,156 +7819,78 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
         for (size_t i = 0; any_list && i < m && !has_list; ++i) has_list = is_list(b + i);
         for (size_t i = 0; i < m; ++i)
             if (kind[b + i] > SGA_KIND_REVOKE) return SGA_EINVAL;
+        // the lane: k_lsmall for a small chunk, k_lseq for inbound events under a SystemRule check, else the pipeline
+        const bool seq_lane = has_in && sys.check;
+        const bool small = m <= small_max && !seq_lane && (!has_list || npvals <= kSmallWords);
 #ifdef SGA_TEST_HOOKS
         g_hook_chunk.counters = sc.counters;
         g_hook_chunk.cbt_ctl = sc.cbt_ctl;
         g_hook_chunk.stream = stream;
-        g_hook_chunk.small = m <= small_max && !(has_in && sys.check) && (!has_list || npvals <= kSmallWords);
+        g_hook_chunk.small = small;
         g_hook_chunk.tiled = false;
         g_hook_chunk.events = (uint32_t)m;
         ++g_hook_chunk.chunks;
 #endif
-        if (m <= small_max && !(has_in && sys.check) && (!has_list || npvals <= kSmallWords)) {
-            if (const int rc = submit_small(kind + b, resource + b, acquire + b, flags ? flags + b : nullptr,
-                                            rt ? rt + b : nullptr, param ? param + b : nullptr, off.data(), lo,
-                                            (uint32_t)m, decision + b, wait_ms ? wait_ms + b : nullptr,
-                                            has_list ? pvals : nullptr, has_list ? npvals : 0,
-                                            origin ? origin + b : nullptr, context ? context + b : nullptr,
-                                            parent ? parent + b : nullptr)) {
-                seq += m;  // a chunk that failed part-way keeps its sequence numbers (pair births)
-                return rc;
-            }
-            b += m;
-            seq += m;
-            continue;
-        }
-        SGA_HIP_CHECK(hipMemcpyAsync(d_kind.p, kind + b, m, hipMemcpyHostToDevice, stream));
-        SGA_HIP_CHECK(hipMemcpyAsync(d_resid.p, resource + b, m * 4, hipMemcpyHostToDevice, stream));
-        SGA_HIP_CHECK(hipMemcpyAsync(d_ts.p, off.data(), m * 4, hipMemcpyHostToDevice, stream));
-        SGA_HIP_CHECK(hipMemcpyAsync(d_acq.p, acquire + b, m * 4, hipMemcpyHostToDevice, stream));
-        if (flags) SGA_HIP_CHECK(hipMemcpyAsync(d_flags.p, flags + b, m, hipMemcpyHostToDevice, stream));
-        else SGA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, m, stream));
-        if (rt) SGA_HIP_CHECK(hipMemcpyAsync(d_rt.p, rt + b, m * 8, hipMemcpyHostToDevice, stream));
-        else SGA_HIP_CHECK(hipMemsetAsync(d_rt.p, 0, m * 8, stream));
-        if (param) SGA_HIP_CHECK(hipMemcpyAsync(d_param.p, param + b, m * 8, hipMemcpyHostToDevice, stream));
-        else SGA_HIP_CHECK(hipMemsetAsync(d_param.p, 0, m * 8, stream));
+        Chunk c;
+        c.ts_base = lo;
+        c.m = (uint32_t)m;
+        c.s = stream;
         for (int k = 0; k < kPairKinds; ++k)
-            if (hids[k])
+            if (hids[k]) {
                 SGA_HIP_CHECK(hipMemcpyAsync(ptab[k].ids.p, hids[k] + b, m * 4, hipMemcpyHostToDevice, stream));
-        if (parent)
-            SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent + b, m * 4, hipMemcpyHostToDevice, stream));
-        // AuthoritySlot: the chunk's effective kind, read below wherever the caller's was
-        const uint8_t *const ek = authority_pass(d_kind.p, d_resid.p, ids[kPairOrigin], (uint32_t)m, stream);
-        const bool auth = ek != d_kind.p;
-        // pair nodes exist ahead of every check; a full table refuses the chunk
-        if (pairs)
-            if (const int rc = pair_claim(ek, d_resid.p, ids, (uint32_t)m, nullptr, stream,
-                                          parent ? ptab[kPairContext].parents.p : nullptr))
-                return rc;
-        SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, stream));
-        // per chunk: a probe sequence that overflowed in an earlier (failed) batch must not fail
-        // every later one.  A failed batch has been partly applied (its node and breaker updates
-        // stay); the call reports -ENOMEM.
-        SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, stream));
-        // CacheMap capacity: owners that could pass theirs switch to LRU mode (both paths below)
-        pair_ctx(ids, stream);
-        lru_prepare(ek, d_resid.p, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
-                    any_list ? d_pvals.p : nullptr, (uint32_t)m, stream);
-        const FlowState st = state();
-        const uint32_t nb = (uint32_t)((m + kT - 1) / kT);
-        // kind 2 / 3 events and argument lists stay on the parallel pipeline (their resources replay per resource,
-        // F_SPECIAL); SystemRules read ENTRY_NODE across resources: one lane in arrival order
-        if (has_in && sys.check) {
-            hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, sys, ek,
-                               d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_param.p, (uint32_t)m, d_dec.p,
-                               d_wait.p, has_list ? d_pvals.p : nullptr);
-            SGA_HIP_CHECK(hipGetLastError());
-            if (pairs)
-                pair_apply(ek, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
-                           nullptr, false, stream);
-            if (auth) authority_answer((uint32_t)m, d_dec.p, d_wait.p, stream);
-            SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
-            if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
-            uint32_t ovf = 0;
-            SGA_HIP_CHECK(hipMemcpyAsync(&ovf, d_overflow.p, 4, hipMemcpyDeviceToHost, stream));
-            SGA_HIP_CHECK(hipStreamSynchronize(stream));
-            if (ovf & kOvfMissingEntry) throw HipError(kMissingEntryText, __FILE__, __LINE__);  // SGA_EIO
-            if (ovf) {
-                seq += m;
-                return SGA_ENOMEM;
+                c.ids[k] = ptab[k].ids.p;
             }
-            b += m;
-            seq += m;
-            continue;
+        if (parent) {
+            SGA_HIP_CHECK(hipMemcpyAsync(ptab[kPairContext].parents.p, parent + b, m * 4, hipMemcpyHostToDevice, stream));
+            c.parent = ptab[kPairContext].parents.p;
         }
-        FlowScratch fsc = special_scratch(sc, ek, flags ? d_flags.p : nullptr, param ? d_param.p : nullptr,
-                                          has_list ? d_pvals.p : nullptr, d_resid.p);
-        const uint64_t *evp = fsc.ev_param;
-        hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, stream, st, fsc, ek, d_resid.p, d_ts.p, lo, d_acq.p,
-                           d_flags.p, param ? d_param.p : nullptr, (uint32_t)m, sc.keys[0], sc.pay[0], d_dec.p, d_wait.p);
-        const int np = radix_sort_pairs(sc.keys[0], sc.pay[0], sc.keys[1], sc.pay[1], m, bits, sc.radix, stream);
-        const uint32_t *keys = sc.keys[np & 1];
-        const Payload *pay = sc.pay[np & 1];
-        const uint32_t ntiles = (uint32_t)((m + kTileElems - 1) / kTileElems);
-        hipLaunchKernelGGL(k_lruns_up, dim3(ntiles), dim3(kT), 0, stream, keys, pay, (uint32_t)m, nres,
-                           (LAgg *)sc.tile_agg, sc.tile_valid);
-        hipLaunchKernelGGL(k_lruns_tiles, dim3(1), dim3(kT), 0, stream, (const LAgg *)sc.tile_agg, sc.tile_valid, ntiles,
-                           (LAgg *)sc.tile_carry, sc.counters);
-        hipLaunchKernelGGL(k_lruns_down, dim3(ntiles), dim3(kT), 0, stream, keys, pay, d_rt.p, nres,
-                           (const LAgg *)sc.tile_carry, sc);
-        hipLaunchKernelGGL(k_lexits, dim3(ntiles), dim3(kT), 0, stream, pay, d_rt.p, sc);
-        const uint32_t fthreads = (uint32_t)std::min<size_t>(m, nres);
-        FlowScratch fsc_p = fsc;  // the flows and the per-value segments (pseg off: null)
-        if ((h_prules.empty() && h_cbs.empty()) || !pseg_on()) fsc_p.pseg = nullptr;
-        hipLaunchKernelGGL(k_lflows, dim3((fthreads + kT - 1) / kT), dim3(kT), 0, stream, st,
-                           (int64_t)cfg.statistic_max_rt, fsc_p, pay, keys, lo, d_rt.p, evp, d_dec.p, d_wait.p);
-        if (has_groups)  // the RELATE groups k_lflows left to a wave each
-            hipLaunchKernelGGL(k_lgroup, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, (uint32_t)(m / kGroupEvents)))),
-                               dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo, d_rt.p, d_dec.p,
-                               d_wait.p);
-        launch_pseg(st, fsc_p, pay, keys, lo, d_rt.p, evp, d_dec.p, d_wait.p, (uint32_t)m, stream);
-        if (st.lru_res) {
-            hipLaunchKernelGGL(k_llru, dim3(64), dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo,
-                               d_rt.p, evp, d_dec.p, d_wait.p);
-            hipLaunchKernelGGL(k_llru_ps, dim3(256), dim3(128), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo,
-                               evp, d_dec.p, d_wait.p);
+        int rc;
+        if (small) {
+            rc = submit_small(c, kind + b, resource + b, acquire + b, flags ? flags + b : nullptr, rt ? rt + b : nullptr,
+                              param ? param + b : nullptr, off.data(), decision + b, wait_ms ? wait_ms + b : nullptr,
+                              has_list ? pvals : nullptr, has_list ? npvals : 0);
+        } else {
+            SGA_HIP_CHECK(hipMemcpyAsync(d_kind.p, kind + b, m, hipMemcpyHostToDevice, stream));
+            SGA_HIP_CHECK(hipMemcpyAsync(d_resid.p, resource + b, m * 4, hipMemcpyHostToDevice, stream));
+            SGA_HIP_CHECK(hipMemcpyAsync(d_ts.p, off.data(), m * 4, hipMemcpyHostToDevice, stream));
+            SGA_HIP_CHECK(hipMemcpyAsync(d_acq.p, acquire + b, m * 4, hipMemcpyHostToDevice, stream));
+            if (flags) SGA_HIP_CHECK(hipMemcpyAsync(d_flags.p, flags + b, m, hipMemcpyHostToDevice, stream));
+            else SGA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, m, stream));
+            if (rt) SGA_HIP_CHECK(hipMemcpyAsync(d_rt.p, rt + b, m * 8, hipMemcpyHostToDevice, stream));
+            else SGA_HIP_CHECK(hipMemsetAsync(d_rt.p, 0, m * 8, stream));
+            if (param) SGA_HIP_CHECK(hipMemcpyAsync(d_param.p, param + b, m * 8, hipMemcpyHostToDevice, stream));
+            else SGA_HIP_CHECK(hipMemsetAsync(d_param.p, 0, m * 8, stream));
+            c.kind_in = d_kind.p;
+            c.resource = d_resid.p;
+            c.ts_off = d_ts.p;
+            c.acquire = d_acq.p;
+            c.flags = d_flags.p;
+            c.rt = d_rt.p;
+            c.param = d_param.p;
+            c.pvals = has_list ? d_pvals.p : nullptr;
+            c.decision = d_dec.p;
+            c.wait_ms = d_wait.p;
+            rc = chunk_prologue(c, false);
+            if (!rc) {
+                if (seq_lane) chunk_seq(c);
+                else chunk_pipeline(c, has_in);
+                chunk_epilogue(c, false);
+                SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
+                if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
+                uint32_t ovf = 0;
+                SGA_HIP_CHECK(hipMemcpyAsync(&ovf, d_overflow.p, 4, hipMemcpyDeviceToHost, stream));
+                SGA_HIP_CHECK(hipStreamSynchronize(stream));
+                rc = host_result(ovf);
+                if (!rc && !seq_lane) debug_size_check();
+            }
         }
-        hipLaunchKernelGGL(k_lwsum, dim3((unsigned)((m / 64 + 3) / 4 + 1)), dim3(256), 0, stream, st, fsc, pay);
-        for (int rl = 0; rl < 2; ++rl)
-            hipLaunchKernelGGL(rl ? k_lwave<1> : k_lwave<0>,
-                               dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, (uint32_t)(m / 4096)))),
-                               dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo, d_rt.p, evp,
-                               d_dec.p, d_wait.p, lwave_prof());
-        print_lwave_prof(stream);
-        hipLaunchKernelGGL(k_lheavy, dim3(std::max<uint32_t>(1, std::min<uint32_t>(1024, (uint32_t)(m / kHeavyEvents)))),
-                           dim3(64), 0, stream, st, (int64_t)cfg.statistic_max_rt, fsc, pay, lo, d_rt.p, evp,
-                           d_dec.p, d_wait.p, heavy_prof());
-        if (heavy_prof()) print_heavy_prof();
-        hipLaunchKernelGGL(k_lresults, dim3(nb), dim3(kT), 0, stream, st, fsc, pay, d_dec.p, d_wait.p);
-        if (has_in)  // ENTRY_NODE statistics of the inbound events
-            hipLaunchKernelGGL(k_entry_stats, dim3(1), dim3(kEnTile), 0, stream, st, (int64_t)cfg.statistic_max_rt,
-                               ek, d_resid.p, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m);
-        SGA_HIP_CHECK(hipGetLastError());
-        if (pairs)  // pair-node statistics from the finished decisions
-            pair_apply(ek, d_resid.p, ids, d_ts.p, lo, d_acq.p, d_flags.p, d_rt.p, d_dec.p, (uint32_t)m,
-                       nullptr, false, stream);
-        if (auth) authority_answer((uint32_t)m, d_dec.p, d_wait.p, stream);
-        SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
-        if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
-        uint32_t ovf = 0;
-        SGA_HIP_CHECK(hipMemcpyAsync(&ovf, d_overflow.p, 4, hipMemcpyDeviceToHost, stream));
-        SGA_HIP_CHECK(hipStreamSynchronize(stream));
-        if (ovf & kOvfMissingEntry) throw HipError(kMissingEntryText, __FILE__, __LINE__);  // SGA_EIO
-        if (ovf) {  // parameter maps full: the chunk is partly applied and keeps its sequence numbers
-            seq += m;
-            return SGA_ENOMEM;
-        }
-        debug_size_check();
+        seq += m;  // a chunk that reached its prologue keeps its sequence numbers (stamps, pair births), failed or not
+        if (rc) return rc;
         b += m;
-        seq += m;
     }
     return 0;
 }
+
 
 // SGA_SIZE_CHECK=1 (diagnostics only): after each host batch, every free-mode owner's kept present count
 // against a count of its present map keys
@@ -7958,8 +7937,6 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
                               const uint32_t *d_parent_in) {
     if (!nres || (d_origin_in && !ptab[kPairOrigin].n_ids) || (d_context_in && !ptab[kPairContext].n_ids))
         return SGA_EINVAL;
-    const uint32_t *ids[kPairKinds] = {d_origin_in, d_context_in};
-    const bool pairs = d_origin_in || d_context_in;
     if (n == 0) return 0;
     if (n > cfg.max_batch) return SGA_ERANGE;
     if (const int rc = ensure_scratch()) return rc;
@@ -7968,90 +7945,43 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
         d_gate.alloc(2);
         SGA_HIP_CHECK(hipMemsetAsync(d_gate.p, 0, 8, s));
     }
-    const uint32_t m = (uint32_t)n;
-    int bits = 1;
-    while (((uint64_t)1 << bits) < (uint64_t)nres + 1) ++bits;
     // absent optional columns read as zeros
     if (!d_rt_in) SGA_HIP_CHECK(hipMemsetAsync(d_rt.p, 0, n * 8, s));
     if (!d_param_in) SGA_HIP_CHECK(hipMemsetAsync(d_param.p, 0, n * 8, s));
     if (!d_flags_in) SGA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, n, s));
-    const int64_t *rt_p = d_rt_in ? d_rt_in : d_rt.p;
-    const uint64_t *param_p = d_param_in ? d_param_in : d_param.p;
-    const uint8_t *flags_p = d_flags_in ? d_flags_in : d_flags.p;
-    int32_t *wait_p = d_wait ? d_wait : this->d_wait.p;
-    SGA_HIP_CHECK(hipMemsetAsync(sc.counters, 0, 64, s));
-    SGA_HIP_CHECK(hipMemsetAsync(d_overflow.p, 0, 4, s));
+    Chunk c;
+    c.kind_in = d_kind_in;  // only read: an effective kind goes to the engine's own array
+    c.resource = d_resource;
+    c.ts_off = d_ts_off;
+    c.ts_base = ts_base;
+    c.acquire = d_acquire;
+    c.flags = d_flags_in ? d_flags_in : d_flags.p;
+    c.rt = d_rt_in ? d_rt_in : d_rt.p;
+    c.param = d_param_in ? d_param_in : d_param.p;
+    c.pvals = d_param_values;
+    c.ids[kPairOrigin] = d_origin_in;
+    c.ids[kPairContext] = d_context_in;
+    c.parent = d_parent_in;
+    c.decision = d_decision;
+    c.wait_ms = d_wait ? d_wait : this->d_wait.p;
+    c.m = (uint32_t)n;
+    c.gate = d_gate.p;
+    c.s = s;
+    // the gate validates the chunk ahead of the prologue, whose pair claim may close it
     SGA_HIP_CHECK(hipMemsetAsync(d_gate.p, 0, 4, s));
-    const uint32_t nb = (m + kT - 1) / kT;
-    const uint32_t gb = std::min<uint32_t>(nb, 1024);
-    hipLaunchKernelGGL(k_lgate, dim3(gb), dim3(kT), 0, s, d_kind_in, d_resource, d_acquire, flags_p, param_p, m, nres,
+    const uint32_t gb = std::min<uint32_t>((c.m + kT - 1) / kT, 1024);
+    hipLaunchKernelGGL(k_lgate, dim3(gb), dim3(kT), 0, s, c.kind_in, c.resource, c.acquire, c.flags, c.param, c.m, nres,
                        (int)sys.check, (uint64_t)(d_param_values ? n_values : 0), d_gate.p, d_param_values);
-    // AuthoritySlot: the chunk's effective kind in the engine's own array (the caller's buffer is only read; the gate
-    // has validated it), read below wherever the caller's was
-    const uint8_t *const d_kind_c = d_kind_in;
-    d_kind_in = authority_pass(d_kind_c, d_resource, d_origin_in, m, s);
-    if (pairs)  // pair nodes exist ahead of every check; a full table or a bad id closes the gate
-        if (const int rc = pair_claim(d_kind_in, d_resource, ids, m, d_gate.p, s, d_parent_in)) return rc;
-    pair_ctx(ids, s);
-    lru_prepare(d_kind_in, d_resource, flags_p, param_p, d_param_values, m, s);  // CacheMap capacity
-    FlowState st = state();
-    st.gate = d_gate.p;
-    FlowScratch gsc = special_scratch(sc, d_kind_in, flags_p, param_p, d_param_values, d_resource);
-    gsc.gate = d_gate.p;
-    hipLaunchKernelGGL(k_lclassify, dim3(nb), dim3(kT), 0, s, st, gsc, d_kind_in, d_resource, d_ts_off, ts_base, d_acquire,
-                       flags_p, param_p, m, gsc.keys[0], gsc.pay[0], d_decision, wait_p);
-    const uint64_t *evp = gsc.ev_param;  // what the parallel kernels read as the event's parameter
-    const int np = radix_sort_pairs(gsc.keys[0], gsc.pay[0], gsc.keys[1], gsc.pay[1], m, bits, gsc.radix, s);
-    const uint32_t *keys = gsc.keys[np & 1];
-    const Payload *pay = gsc.pay[np & 1];
-    const uint32_t ntiles = (m + kTileElems - 1) / kTileElems;
-    hipLaunchKernelGGL(k_lruns_up, dim3(ntiles), dim3(kT), 0, s, keys, pay, m, nres, (LAgg *)gsc.tile_agg,
-                       gsc.tile_valid);
-    hipLaunchKernelGGL(k_lruns_tiles, dim3(1), dim3(kT), 0, s, (const LAgg *)gsc.tile_agg, gsc.tile_valid, ntiles,
-                       (LAgg *)gsc.tile_carry, gsc.counters);
-    hipLaunchKernelGGL(k_lruns_down, dim3(ntiles), dim3(kT), 0, s, keys, pay, rt_p, nres, (const LAgg *)gsc.tile_carry,
-                       gsc);
-    hipLaunchKernelGGL(k_lexits, dim3(ntiles), dim3(kT), 0, s, pay, rt_p, gsc);
-    const uint32_t fthreads = std::min<uint32_t>(m, nres);
-    if ((h_prules.empty() && h_cbs.empty()) || !pseg_on()) gsc.pseg = nullptr;
-    hipLaunchKernelGGL(k_lflows, dim3((fthreads + kT - 1) / kT), dim3(kT), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc,
-                       pay, keys, ts_base, rt_p, evp, d_decision, wait_p);
-    if (has_groups)  // known on the host from the rule load: no launch without RELATE rules
-        hipLaunchKernelGGL(k_lgroup, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, m / kGroupEvents))), dim3(64), 0,
-                           s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p, d_decision, wait_p);
-    launch_pseg(st, gsc, pay, keys, ts_base, rt_p, evp, d_decision, wait_p, m, s);
-    if (st.lru_res) {
-        hipLaunchKernelGGL(k_llru, dim3(64), dim3(64), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p,
-                           evp, d_decision, wait_p);
-        hipLaunchKernelGGL(k_llru_ps, dim3(256), dim3(128), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base,
-                           evp, d_decision, wait_p);
-    }
-    hipLaunchKernelGGL(k_lwsum, dim3((m / 64 + 3) / 4 + 1), dim3(256), 0, s, st, gsc, pay);
-    for (int rl = 0; rl < 2; ++rl)
-        hipLaunchKernelGGL(rl ? k_lwave<1> : k_lwave<0>, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, m / 4096))),
-                           dim3(64), 0, s, st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p, evp, d_decision,
-                           wait_p, lwave_prof());
-    print_lwave_prof(s);
-    hipLaunchKernelGGL(k_lheavy, dim3(std::max<uint32_t>(1, std::min<uint32_t>(1024, m / kHeavyEvents))), dim3(64), 0, s,
-                       st, (int64_t)cfg.statistic_max_rt, gsc, pay, ts_base, rt_p, evp, d_decision, wait_p,
-                       heavy_prof());
-        if (heavy_prof()) print_heavy_prof();
-    hipLaunchKernelGGL(k_lresults, dim3(nb), dim3(kT), 0, s, st, gsc, pay, d_decision, wait_p);
-    hipLaunchKernelGGL(k_entry_stats, dim3(1), dim3(kEnTile), 0, s, st, (int64_t)cfg.statistic_max_rt, d_kind_in,
-                       d_resource, d_ts_off, ts_base, d_acquire, flags_p, rt_p, d_decision, m);
-    // arrival-order chunks (inbound events under system rules): k_lseq acts only when the gate says so
-    hipLaunchKernelGGL(k_lseq, dim3(1), dim3(64), 0, s, st, (int64_t)cfg.statistic_max_rt, sys, d_kind_in,
-                       d_resource, d_ts_off, ts_base, d_acquire, flags_p, rt_p, param_p, m, d_decision, wait_p,
-                       d_param_values);
-    if (pairs)  // pair-node statistics from the finished decisions (either path's)
-        pair_apply(d_kind_in, d_resource, ids, d_ts_off, ts_base, d_acquire, flags_p, rt_p, d_decision, m, d_gate.p,
-                   false, s);
-    if (d_kind_in != d_kind_c) authority_answer(m, d_decision, wait_p, s);  // ahead of k_lfail: a refused chunk answers -1
-    hipLaunchKernelGGL(k_lfail, dim3(gb), dim3(kT), 0, s, d_gate.p, d_overflow.p, d_gate.p + 1, m, d_decision, wait_p);
+    if (const int rc = chunk_prologue(c, false)) return rc;
+    chunk_pipeline(c, true);
+    chunk_epilogue(c, false);
+    hipLaunchKernelGGL(k_lfail, dim3(gb), dim3(kT), 0, s, d_gate.p, d_overflow.p, d_gate.p + 1, c.m, c.decision,
+                       c.wait_ms);
     SGA_HIP_CHECK(hipGetLastError());
     seq += n;
     return 0;
 }
+
 
 int FlowEngine::device_status() {
     if (!d_gate.p) return 0;
@@ -8274,28 +8204,31 @@ PairTabs FlowEngine::pstate() const {
 
 // The chunk's PairCtx, when the loaded rules hold pair-ruled resources (ids[k] null: every event has id 0 of that
 // kind, so only rules that need none apply)
-void FlowEngine::pair_ctx(const uint32_t *const ids[kPairKinds], hipStream_t s) {
+void FlowEngine::pair_ctx(const Chunk &c) {
     if (!has_pair_rules) return;
     const PairCtx h{pstate(),
-                    {ids[0], ids[1]},
+                    {c.ids[0], c.ids[1]},
                     {ptab[0].slot.p, ptab[1].slot.p},
                     d_rule_lim.p,
                     d_rule_ctx.p,
                     d_oruled.p,
                     (uint64_t)seq};
-    hipLaunchKernelGGL(k_set_octx, dim3(1), dim3(1), 0, s, d_octx.p, h);
+    hipLaunchKernelGGL(k_set_octx, dim3(1), dim3(1), 0, c.s, d_octx.p, h);
     SGA_HIP_CHECK(hipGetLastError());
 }
 
-int FlowEngine::pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
-                           uint32_t m, uint32_t *gate, hipStream_t s, const uint32_t *parent) {
+int FlowEngine::pair_claim(const Chunk &c) {
+    const uint32_t *const *ids = c.ids;
+    const uint32_t m = c.m;
+    uint32_t *gate = c.gate;
+    hipStream_t s = c.s;
     const PairTabs pt = pstate();
     const PairIds pi{{ids[0], ids[1]}, {ptab[0].slot.p, ptab[1].slot.p}};
     const uint32_t kinds = (ids[0] ? 1u : 0u) | (ids[1] ? 2u : 0u);
     uint32_t rslots = 0;
     for (int k = 0; k < kPairKinds; ++k)
         if (ids[k]) rslots = std::max(rslots, ptab[k].slots);
-    if (!ids[kPairContext]) parent = nullptr;  // no event of the chunk creates a DefaultNode
+    const uint32_t *parent = ids[kPairContext] ? c.parent : nullptr;  // else no event creates a DefaultNode
     // the birth pass: only for a chunk that carries parents, once every birth of the chunk is known
     auto births = [&]() {
         if (!parent) return;
@@ -8303,7 +8236,7 @@ int FlowEngine::pair_claim(const uint8_t *kind, const uint32_t *resource, const 
                            ptab[kPairContext].slot.p, parent, m, (uint64_t)seq, gate);
     };
     SGA_HIP_CHECK(hipMemsetAsync(d_pctl.p, 0, 8, s));  // the chunk's error bits and long segments
-    hipLaunchKernelGGL(k_oclaim, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, kind, resource, m, nres,
+    hipLaunchKernelGGL(k_oclaim, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, c.kind, c.resource, m, nres,
                        (uint64_t)seq, gate, parent);
     if (gate) {  // device entry: the gate refuses the chunk, k_lfail reports it
         hipLaunchKernelGGL(k_orollback, dim3((rslots + kT - 1) / kT), dim3(kT), 0, s, pt, kinds, (uint64_t)seq, gate);
@@ -8325,16 +8258,17 @@ int FlowEngine::pair_claim(const uint8_t *kind, const uint32_t *resource, const 
     return (err & kPairBadId) ? SGA_EINVAL : SGA_ENOMEM;
 }
 
-void FlowEngine::pair_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
-                            const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
-                            const int64_t *rt, const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq_lane,
-                            hipStream_t s) {
+void FlowEngine::pair_apply(const Chunk &c, bool seq_lane) {
+    const uint32_t *const *ids = c.ids, *gate = c.gate;
+    const uint32_t m = c.m;
+    hipStream_t s = c.s;
     const PairTabs pt = pstate();
     const PairIds pi{{ids[0], ids[1]}, {ptab[0].slot.p, ptab[1].slot.p}};
     const int64_t max_rt = (int64_t)cfg.statistic_max_rt;
     if (seq_lane) {
-        hipLaunchKernelGGL(k_oseq, dim3(1), dim3(64), 0, s, pt, pi, max_rt, nres, (uint64_t)seq, kind, resource, ts_off,
-                           ts_base, acquire, flags, rt, decision, m, has_pair_rules ? d_oruled.p : nullptr);
+        hipLaunchKernelGGL(k_oseq, dim3(1), dim3(64), 0, s, pt, pi, max_rt, nres, (uint64_t)seq, c.kind, c.resource,
+                           c.ts_off, c.ts_base, c.acquire, c.flags, c.rt, c.decision, m,
+                           has_pair_rules ? d_oruled.p : nullptr);
         SGA_HIP_CHECK(hipGetLastError());
         return;
     }
@@ -8345,17 +8279,15 @@ void FlowEngine::pair_apply(const uint8_t *kind, const uint32_t *resource, const
     uint32_t *k0 = two ? d_pkeys[0].p : sc.keys[0], *k1 = two ? d_pkeys[1].p : sc.keys[1];
     Payload *p0 = two ? d_ppay[0].p : sc.pay[0], *p1 = two ? d_ppay[1].p : sc.pay[1];
     RadixScratch rs2{nullptr, nullptr, d_phist[0].p, d_phist[1].p, d_ppart.p};
-    hipLaunchKernelGGL(k_oelems, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, nres, (uint64_t)seq, kind, resource,
-                       ts_off, acquire, flags, decision, m, k0, p0, gate, has_pair_rules ? d_oruled.p : nullptr);
-    int bits = 1;
-    while (((uint64_t)1 << bits) < (uint64_t)pt.total + 1) ++bits;
-    const int np = radix_sort_pairs(k0, p0, k1, p1, ne, bits, two ? rs2 : sc.radix, s);
+    hipLaunchKernelGGL(k_oelems, dim3((m + kT - 1) / kT), dim3(kT), 0, s, pt, pi, nres, (uint64_t)seq, c.kind, c.resource,
+                       c.ts_off, c.acquire, c.flags, c.decision, m, k0, p0, gate, has_pair_rules ? d_oruled.p : nullptr);
+    const int np = radix_sort_pairs(k0, p0, k1, p1, ne, key_bits(pt.total), two ? rs2 : sc.radix, s);
     const uint32_t *keys = (np & 1) ? k1 : k0;
     const Payload *pay = (np & 1) ? p1 : p0;
-    hipLaunchKernelGGL(k_oshort, dim3((ne + kT - 1) / kT), dim3(kT), 0, s, pt, max_rt, keys, pay, ne, d_olong.p, ts_base,
-                       rt, gate);
+    hipLaunchKernelGGL(k_oshort, dim3((ne + kT - 1) / kT), dim3(kT), 0, s, pt, max_rt, keys, pay, ne, d_olong.p,
+                       c.ts_base, c.rt, gate);
     hipLaunchKernelGGL(k_olong, dim3(std::max<uint32_t>(1, std::min<uint32_t>(2048, ne / kOriginLong))), dim3(kOriginT),
-                       0, s, pt, max_rt, keys, pay, d_olong.p, ts_base, rt, gate);
+                       0, s, pt, max_rt, keys, pay, d_olong.p, c.ts_base, c.rt, gate);
     SGA_HIP_CHECK(hipGetLastError());
 }
 
@@ -8504,17 +8436,18 @@ int FlowEngine::load_authority_rules(const uint32_t *resource, const int32_t *st
     return (int)kept;
 }
 
-const uint8_t *FlowEngine::authority_pass(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin,
-                                          uint32_t m, hipStream_t s) {
-    if (!auth_dev || !origin) return kind;
-    hipLaunchKernelGGL(k_authority, dim3((m + kT - 1) / kT), dim3(kT), 0, s, auth_state(), kind, resource, origin, m,
-                       d_ekind.p, d_aturned.p);
+void FlowEngine::authority_pass(Chunk &c) {
+    c.kind = c.kind_in;
+    if (!auth_dev || !c.ids[kPairOrigin]) return;
+    hipLaunchKernelGGL(k_authority, dim3((c.m + kT - 1) / kT), dim3(kT), 0, c.s, auth_state(), c.kind_in, c.resource,
+                       c.ids[kPairOrigin], c.m, d_ekind.p, d_aturned.p);
     SGA_HIP_CHECK(hipGetLastError());
-    return d_ekind.p;
+    c.kind = d_ekind.p;
 }
 
-void FlowEngine::authority_answer(uint32_t m, int8_t *decision, int32_t *wait_ms, hipStream_t s) {
-    hipLaunchKernelGGL(k_authority_answer, dim3((m + kT - 1) / kT), dim3(kT), 0, s, d_aturned.p, m, decision, wait_ms);
+void FlowEngine::authority_answer(const Chunk &c) {
+    hipLaunchKernelGGL(k_authority_answer, dim3((c.m + kT - 1) / kT), dim3(kT), 0, c.s, d_aturned.p, c.m, c.decision,
+                       c.wait_ms);
     SGA_HIP_CHECK(hipGetLastError());
 }
 

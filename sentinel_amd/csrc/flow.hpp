@@ -325,6 +325,27 @@ struct FlowScratch {
 
 void print_heavy_prof();  // SGA_HEAVY_PROF=1 diagnostics (flow.hip)
 
+// One chunk of the local path as every host-side stage sees it (never passed to a kernel): device columns of m
+// events.  flags, rt and param are never null (an absent column is a zero-filled staging buffer).
+struct Chunk {
+    const uint8_t *kind_in = nullptr;  // the caller's kind
+    const uint8_t *kind = nullptr;     // the effective kind (AuthoritySlot), set by chunk_prologue
+    const uint32_t *resource = nullptr, *ts_off = nullptr;
+    int64_t ts_base = 0;
+    const int32_t *acquire = nullptr;
+    const uint8_t *flags = nullptr;
+    const int64_t *rt = nullptr;
+    const uint64_t *param = nullptr, *pvals = nullptr;  // pvals: null when no event of the chunk names a list
+    const uint32_t *ids[kPairKinds] = {nullptr, nullptr};  // null: every event has id 0 of that kind
+    const uint32_t *parent = nullptr;                      // enclosing resources of the DefaultNodes it creates
+    int8_t *decision = nullptr;
+    int32_t *wait_ms = nullptr;
+    uint32_t m = 0;
+    uint32_t *gate = nullptr;  // device entry: FlowEngine::d_gate; null on the host entries
+    hipStream_t s = nullptr;
+    bool pairs() const { return ids[0] || ids[1]; }
+    bool turned() const { return kind != kind_in; }  // k_authority ran: authority_answer writes its decisions
+};
 
 struct FlowEngine {
     sga_config cfg{};
@@ -354,12 +375,11 @@ struct FlowEngine {
     uint64_t seq = 0;               // events submitted so far (stamps)
     void lru_sync_rules();          // per-id / per-slot arrays after a parameter-rule load
     // parameter-only resources per (rule, value) segment, after k_lflows took their flows (flow.hip k_pseg_*)
-    void launch_pseg(const FlowState &st, const FlowScratch &g, const Payload *pay, const uint32_t *keys,
-                     int64_t ts_base, const int64_t *rt, const uint64_t *param, int8_t *decision, int32_t *wait_ms,
-                     uint32_t m, hipStream_t s);
+    void launch_pseg(const Chunk &c, const FlowState &st, const FlowScratch &g, const Payload *pay,
+                     const uint32_t *keys);
     void debug_size_check();  // SGA_SIZE_CHECK=1 diagnostics
-    void lru_prepare(const uint8_t *kind, const uint32_t *resource, const uint8_t *flags, const uint64_t *param,
-                     const uint64_t *pvals, uint32_t n, hipStream_t s);  // count pass + switches, before a batch
+    bool lru_counts() const { return d_psize.p && !h_prules.empty(); }  // lru_prepare launches its count pass
+    void lru_prepare(const Chunk &c);  // count pass + switches, before a batch
     int lru_error(hipStream_t s);   // sticky queue errors (host wait)
     CParamState cparam_st{};      // set before each batch (the engine's cluster parameter state)
     bool has_cluster_prules = false;
@@ -423,21 +443,29 @@ struct FlowEngine {
                const uint8_t *flags, const int64_t *rt, const uint64_t *param, size_t n, int8_t *decision,
                int32_t *wait_ms, const uint64_t *pvals = nullptr, size_t npvals = 0,
                const uint32_t *origin = nullptr, const uint32_t *context = nullptr, const uint32_t *parent = nullptr);
-    FlowScratch special_scratch(const FlowScratch &base, const uint8_t *d_kind_in, const uint8_t *d_flags_in,
-                                const uint64_t *d_param_in, const uint64_t *d_pvals, const uint32_t *d_resource_in);
     DevBuf<uint64_t> d_pvals;  // values of Collection / array arguments (SGA_EV_PARAM_LIST)
-    // the same over device buffers, asynchronous on s: one chunk of n <= max_batch events
+    // The stages of a chunk, each written once for the three entries.  chunk_prologue: the
+    // authority pass (the one place that decides c.kind), the pair claim (its refusal is returned), the control
+    // word clears, pair_ctx, lru_prepare; small: k_lsmall decides the chunk (no dispatch counts to clear).
+    // chunk_pipeline: special_scratch to k_entry_stats (gate null: k_entry_stats only when inbound); with a gate
+    // it ends in chunk_seq, for the gate to choose.  chunk_seq: k_lseq.  chunk_epilogue: pair_apply
+    // (seq_lane: k_oseq), then authority_answer.  host_result: the host entries' rule for the overflow word.
+    int chunk_prologue(Chunk &c, bool small);
+    void chunk_pipeline(const Chunk &c, bool inbound);
+    void chunk_seq(const Chunk &c);
+    void chunk_epilogue(const Chunk &c, bool seq_lane);
+    static int host_result(uint32_t ovf);
+    FlowScratch special_scratch(const Chunk &c);  // advances epoch: once per pipeline chunk, in no other lane
     // small host batches (<= kSmallEvents events, <= kSmallWords argument words, no SystemRule check): one
     // packed page-locked copy each way and one replay kernel (k_lsmall) instead of the pipeline
     static constexpr uint32_t kSmallEvents = 1024, kSmallWords = 16384;
     uint32_t small_max = kSmallEvents;  // sga_set_small_batch (0: off)
     PinnedBuf h_small;
-    DevBuf<uint8_t> d_small;
-    int submit_small(const uint8_t *kind, const uint32_t *resource, const int32_t *acquire, const uint8_t *flags,
-                     const int64_t *rt, const uint64_t *param, const uint32_t *ts_off, int64_t lo, uint32_t m,
-                     int8_t *decision, int32_t *wait_ms, const uint64_t *pvals, size_t npvals,
-                     const uint32_t *origin = nullptr, const uint32_t *context = nullptr,
-                     const uint32_t *parent = nullptr);
+    // c: the chunk's ids, parent, ts_base, m and stream; its columns are set here, to the packed buffer's
+    int submit_small(Chunk c, const uint8_t *kind, const uint32_t *resource, const int32_t *acquire,
+                     const uint8_t *flags, const int64_t *rt, const uint64_t *param, const uint32_t *ts_off,
+                     int8_t *decision, int32_t *wait_ms, const uint64_t *pvals, size_t npvals);
+    // the same as submit over device buffers, asynchronous on s: one chunk of n <= max_batch events
     int submit_device(const uint8_t *d_kind, const uint32_t *d_resource, int64_t ts_base, const uint32_t *d_ts_off,
                       const int32_t *d_acquire, const uint8_t *d_flags, const int64_t *d_rt_in,
                       const uint64_t *d_param_in, size_t n, const uint64_t *d_param_values, size_t n_values,
@@ -466,20 +494,15 @@ struct FlowEngine {
     DevBuf<PairCtx> d_octx;
     DevBuf<uint32_t> d_olist;  // pair_nodes_of: [0] count, then the ids
     bool has_pair_rules = false;
-    // before a chunk's decisions (ids[k] null: every event has id 0)
-    void pair_ctx(const uint32_t *const ids[kPairKinds], hipStream_t s);
+    void pair_ctx(const Chunk &c);  // before a chunk's decisions
     int set_pairs(int kind, uint32_t n, uint32_t max_nodes);
     PairTabs pstate() const;
     // the claim pass of a chunk (ahead of every check): the chunk's pairs find or claim their records.  Host
     // entry (gate null): waits, SGA_ENOMEM when a table is full -- the chunk's claims are then taken back.
-    // parent (device, may be null): the chunk's enclosing resources; the pairs the chunk creates record theirs
-    int pair_claim(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds], uint32_t m,
-                   uint32_t *gate, hipStream_t s, const uint32_t *parent = nullptr);
-    // the statistics pass of a chunk, after its decisions (seq: one lane in arrival order, small chunks)
-    void pair_apply(const uint8_t *kind, const uint32_t *resource, const uint32_t *const ids[kPairKinds],
-                    const uint32_t *ts_off, int64_t ts_base, const int32_t *acquire, const uint8_t *flags,
-                    const int64_t *rt, const int8_t *decision, uint32_t m, const uint32_t *gate, bool seq,
-                    hipStream_t s);
+    // c.parent (may be null): the chunk's enclosing resources; the pairs the chunk creates record theirs
+    int pair_claim(const Chunk &c);
+    // the statistics pass of a chunk, after its decisions (seq_lane: one lane in arrival order, small chunks)
+    void pair_apply(const Chunk &c, bool seq_lane);
     int query_pair(int kind, uint32_t resource, uint32_t id, int64_t now, sga_node_view *out);
     int pair_nodes_of(int kind, uint32_t resource, uint32_t *ids, size_t cap, size_t *n);
     // sga_query_tree: k_tree_rows over the context table, rows sorted by (context, resource)
@@ -514,10 +537,9 @@ struct FlowEngine {
     int load_authority_rules(const uint32_t *resource, const int32_t *strategy, const uint32_t *list_off, size_t n,
                              const uint32_t *origin_ids);
     int authority_check(const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass);
-    // the chunk's effective kind (kind itself when no rule is on the device or the chunk has no origin array)
-    const uint8_t *authority_pass(const uint8_t *kind, const uint32_t *resource, const uint32_t *origin, uint32_t m,
-                                  hipStream_t s);
-    void authority_answer(uint32_t m, int8_t *decision, int32_t *wait_ms, hipStream_t s);
+    // sets c.kind: the chunk's effective kind (c.kind_in when no rule is on the device or it has no origin array)
+    void authority_pass(Chunk &c);
+    void authority_answer(const Chunk &c);
     SysDev sys{0, 0, 0, 0, 1.7976931348623157e308, 1.7976931348623157e308, 1.7976931348623157e308, INT64_MAX,
                INT64_MAX, -1.0, -1.0};
     DevBuf<sga_metric_node> d_metrics;

@@ -8,6 +8,7 @@ engine with the same rules minus authority, fed the pre-marked stream (the turne
 agree everywhere except 6 against 0 at the turned positions.  Each stream is built once and asserts on the CPU
 that it holds authority blocks, authority passes and at least one other kind of block."""
 import functools
+import heapq
 import json
 from urllib.parse import quote
 
@@ -282,6 +283,91 @@ def test_device_entry():
 def test_arrival_order_lane_counts_entry_node_and_is_not_system_checked():
     tr = _auth_trace("inbound")
     _form(tr, 1 << 15, 0, [(0, len(tr["ed"]), AUTH_1)], system=SYSTEM, what="seq")
+
+
+# ------------------------------------------------------------------ 2b: the three host lanes in one call
+LANES = (2048, 2048, 500)  # events per chunk at max_batch 2048: the pipeline, k_lseq (inbound events), k_lsmall
+
+
+@functools.lru_cache(maxsize=None)
+def _lanes_trace():
+    """The mixed workload under AUTH_1 and the blocking SystemRule, one event per step so that the chunk borders
+    fall where LANES puts them: no inbound event in the first and the third chunk, every other entry of the second
+    inbound.  The second chunk's last 150 events (80 ms, rt <= 39) hold no inbound entry, so no inbound exit is
+    left for the third; the exits still due when the stream ends are not part of it.
+    tests/test_authority_host.py asserts what each chunk holds."""
+    h = ot.OriginTrace(MIX_RES, MIX_ORG, MIX_FLOW, MIX_PARAM, MIX_DEGRADE, system=SYSTEM)
+    a = at.AuthorityTrace(h, RES, ORIGINS, AUTH_1)
+    rng = np.random.default_rng(31)
+    w, ow = np.array([3, 2, 2, 2, 1, 2, 2, 2], float), np.array([2, 3, 2, 1, 1, 0.5])
+    ends = np.cumsum(LANES)
+    t = T0 + rng.exponential(1.0)
+    while len(h.ev) < ends[-1]:
+        n, now = len(h.ev), int(t)
+        if h.heap and h.heap[0][0] <= now:  # one exit per step
+            te, _, rid, o, acq, fl, rt, pv = heapq.heappop(h.heap)
+            h.other(1, rid, o, te, acq, fl, rt, pv)
+            continue
+        rid, o = int(rng.choice(len(w), p=w / w.sum())), int(rng.choice(len(ow), p=ow / ow.sum()))
+        hp = rid == 5 and rng.random() < 0.9
+        inb = bool(ends[0] <= n < ends[1] - 150 and rng.random() < 0.5)
+        a.step(rid, o, now, now, int(rng.integers(1, 3)), int(rng.integers(0, 40)), hp,
+               int(rng.integers(0, 6)) if hp else 0, 1 if inb else 0, rng.random() < 0.1)
+        t += rng.exponential(1.0)
+    h.heap.clear()
+    return a.finish(entry=True)
+
+
+def _run_lanes(hook=None):
+    """One host call whose chunks take the pipeline, the arrival-order lane and the small path in turn: what a
+    shared prologue or epilogue could leak from one chunk into the next (the overflow word, the dispatch counts,
+    the effective kind, the epoch, the sequence numbers) would show in the decisions or the nodes."""
+    tr = _lanes_trace()
+    eng, s = _sentinel(MIX_RES, MIX_ORG, LANES[0])  # the small limit stays at its default
+    _load(s, MIX_FLOW, MIX_PARAM, MIX_DEGRADE, SYSTEM)
+    _load_auth(s, AUTH_1)
+    got = _submit(s, tr["st"])
+    forms = hook() if hook else None
+    _same(tr["st"], got, tr["ed"], tr["ew"], "lanes")
+    _nodes(s, tr, MIX_RES, MIX_ORG, "lanes")
+    eng.close()
+    return forms
+
+
+def lanes_child():
+    """Runs in the child process of test_three_lanes_dispatch (the test-only build is loaded)."""
+    import ctypes as C
+
+    from sentinel_amd import _lib
+    fn = _lib.load().sga_test_local_dispatch  # the product library does not have it
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(C.c_uint32), C.c_size_t]
+
+    def hook():
+        out = (C.c_uint32 * 12)()
+        assert fn(out, 12) == 12
+        return [int(x) for x in out]
+
+    print("LANES", json.dumps(_run_lanes(hook)))
+
+
+def test_three_lanes_in_one_call():
+    _run_lanes()
+
+
+def test_three_lanes_dispatch():
+    """The same call under the test-only build: three host chunks since the process began, the last one decided
+    by k_lsmall, 500 events."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = f"import sys; sys.path.insert(0, {root!r}); from tests.test_authority_gpu import lanes_child; lanes_child()"
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SGA_LIB_VARIANT="testhooks"),
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    forms = json.loads([x for x in r.stdout.splitlines() if x.startswith("LANES ")][-1][6:])
+    assert forms[9:12] == [1, LANES[2], 3], forms
 
 
 # ------------------------------------------------------------------ 3: edges

@@ -91,6 +91,33 @@ def test_wrapper_turns_failing_entries_without_an_oracle():
     assert a.step(0, 1, 9, 9) == (0, 0)
 
 
+def test_three_lane_call_holds_what_each_chunk_must_decide():
+    """The stream of test_authority_gpu.py's three-lane case, chunk by chunk as the engine cuts it: inbound events
+    in the second chunk alone (the arrival-order lane; the third stays small), and in every chunk passes, flow
+    blocks, parameter-rule entries and authority-turned entries; system blocks in the second."""
+    import numpy as np
+
+    from tests.test_authority_gpu import LANES, _lanes_trace
+    tr = _lanes_trace()
+    st, ed = tr["st"], tr["ed"]
+    assert len(ed) == sum(LANES) and LANES[0] == LANES[1] > 1024 >= LANES[2]
+    turned = np.zeros(len(ed), bool)
+    turned[tr["turned"]] = True
+    lo = 0
+    for k, n in enumerate(LANES):
+        sl = slice(lo, lo + n)
+        ent = st["kind"][sl] == 0
+        d = ed[sl][ent]
+        inbound = (st["flags"][sl] & 8) != 0
+        assert inbound.any() == (k == 1), k
+        assert (d == 0).sum() >= 50 and (d == 1).sum() >= 10 and turned[sl].sum() >= 10, (k, np.bincount(d))
+        assert (ent & (st["resource"][sl] == 5) & ((st["flags"][sl] & 4) != 0)).sum() >= 10, k
+        assert (st["kind"][sl] == 1).sum() >= 50 and (st["origin"][sl] != 0).sum() >= 100, k
+        assert ((d == 5).sum() >= 10) == (k == 1), (k, np.bincount(d))
+        lo += n
+    assert tr["nodes"][0xFFFFFFFF][0] != [0] * len(tr["nodes"][0xFFFFFFFF][0])  # ENTRY_NODE counted something
+
+
 # ------------------------------------------------------------------ the manager over a stand-in library
 class _Lib:
     """The engine library's entry points the host side calls here, recording the authority load."""
