@@ -811,6 +811,50 @@ int sga_load_authority_rules(sga_engine *e, const uint32_t *resource, const int3
  * pass[i] = 1 / 0.  Touches no state.  Ids out of range: SGA_EINVAL. */
 int sga_authority_check(sga_engine *e, const uint32_t *resource, const uint32_t *origin, size_t n, uint8_t *pass);
 
+/* ---- block log (LogSlot; new entry points only) ---- */
+/* LogSlot (CORE/slots/logger/LogSlot.java:34-47) hands every BlockException to EagleEyeLogUtil.log(resource,
+ * exceptionSimpleName, ruleLimitApp, origin, count), which a StatLogger sums per second into sentinel-block.log.
+ * The engine keeps that sum on the device: once enabled, every chunk of every submit entry (host and device) ends
+ * with one pass that adds the chunk's blocked entries to an engine-resident table of rows.  Logged: events the
+ * caller submitted as SGA_KIND_ENTRY whose decision is SGA_BLOCK_FLOW, _PARAM, _DEGRADE, _SYSTEM or _AUTHORITY.
+ * Not logged: SGA_PASS_WAIT (PriorityWaitException is no BlockException), exits, kind 2 / 3 events (the slot that
+ * threw their block has a LogSlot of its own in front of it), and chunks the device entry refused (-1).
+ * Off by default: an engine that never enables the log launches and allocates nothing for it. */
+#define SGA_TAG_SCALAR 0u  /* tag = the argument's 64-bit key */
+#define SGA_TAG_LIST 1u    /* tag = a 64-bit fold of the list's length and its element keys in order */
+typedef struct sga_block_row {
+    int64_t time_slot;   /* ts - ts % 1000 of the entries (StatLogger's rolling slot at intervalSeconds(1)) */
+    uint64_t tag;        /* SGA_BLOCK_PARAM: args[paramIdx] of the blocking rule (tag_kind); 0 for every other decision */
+    int64_t count;       /* sum of acquire (StatEntry.count(count)) */
+    uint32_t resource;
+    uint32_t origin;     /* 0 when the call had no origin array */
+    uint32_t detail;     /* the block detail wait_ms carried */
+    uint32_t events;     /* number of entries */
+    uint8_t decision;    /* SGA_BLOCK_* */
+    uint8_t tag_kind;    /* SGA_TAG_SCALAR / SGA_TAG_LIST */
+    uint8_t reserved[6]; /* zero: sizeof == 48 */
+} sga_block_row;
+
+/* Turns the log on with room for max_rows rows (0: the default of 65,536; at least 64; rounded up to a power of
+ * two).  Two tuples whose 64-bit hashes collide share a row (as two strings whose 64-bit keys collide share a parameter counter).
+ * Calling it again resizes an empty log; with rows pending: SGA_EINVAL. */
+int sga_block_log_enable(sga_engine *e, uint32_t max_rows);
+
+/* Moves out every row with time_slot + 1000 <= before_ms (INT64_MAX: all), sorted by (time_slot, resource,
+ * decision, detail, origin, tag_kind, tag); *n = their number.  More than cap: SGA_ERANGE, *n = the number needed,
+ * nothing removed, the lost counters neither returned nor cleared.  A drained second that receives further events
+ * gets new rows.  *lost_events / *lost_count (either may be NULL): entries and their acquire sum that found no room
+ * in the table since the last successful drain -- returned and cleared.  Waits for the engine stream.  An engine
+ * without the log: SGA_EINVAL. */
+int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n,
+                        uint64_t *lost_events, int64_t *lost_count);
+
+/* The rule a block detail names, as its index in the array the caller last passed to the matching loader
+ * (SGA_BLOCK_FLOW: sga_load_flow_rules*, whose _origin / _ctx forms reorder; SGA_BLOCK_PARAM: sga_load_param_rules;
+ * SGA_BLOCK_DEGRADE: sga_load_degrade_rules).  Any other decision, an unknown resource or a detail past the
+ * resource's rules: SGA_EINVAL. */
+int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index);
+
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {
     double highest_system_load;

@@ -114,6 +114,14 @@ class SgaTreeRow(C.Structure):
                 ("view", SgaNodeView)]
 
 
+class SgaBlockRow(C.Structure):  # sga_block_row: one aggregated key of the block log
+    _fields_ = [("time_slot", C.c_int64), ("tag", C.c_uint64), ("count", C.c_int64), ("resource", C.c_uint32),
+                ("origin", C.c_uint32), ("detail", C.c_uint32), ("events", C.c_uint32), ("decision", C.c_uint8),
+                ("tag_kind", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+SGA_TAG_SCALAR, SGA_TAG_LIST = 0, 1  # sga_block_row.tag_kind
+
 SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
 
 # sga_query_nodes: the node table, and the flag of clusterNode?type=notZero
@@ -243,6 +251,10 @@ SIGNATURES = {
     "sga_context_nodes_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_load_authority_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sga_authority_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sga_block_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "sga_block_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "sga_block_rule_index": (C.c_int, [C.c_void_p, C.c_int8, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -2665,6 +2665,25 @@ int sga_authority_check(sga_engine *e, const uint32_t *resource, const uint32_t 
     });
 }
 
+int sga_block_log_enable(sga_engine *e, uint32_t max_rows) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.block_log_enable(max_rows);
+    });
+}
+
+int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n,
+                        uint64_t *lost_events, int64_t *lost_count) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.block_log_drain(before_ms, rows, cap, n, lost_events, lost_count);
+    });
+}
+
+int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index) {
+    return guarded(e, [&](Engine &g) { return g.flow.block_rule_index(decision, resource, detail, index); });
+}
+
 int sga_load_system_rules(sga_engine *e, const sga_system_rule *rules, size_t n) {
     if (n && !rules) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) { return g.flow.load_system_rules(rules, n); });

@@ -1334,6 +1334,210 @@ __global__ __launch_bounds__(kT) void k_authority_answer(const uint8_t *__restri
     wait_ms[i] = 0;
 }
 
+// ---- block log (LogSlot.java:34-47 -> EagleEyeLogUtil.log -> StatLogger: a sum per second and key)
+// The 64-bit fold of a Collection / array argument: its length, then its element keys in order
+// (sentinel_amd.block_log.list_tag restates it for the host's parameter texts).
+__device__ __forceinline__ uint64_t blog_list_tag(const uint64_t *vals, uint32_t n) {
+    uint64_t h = splitmix64((uint64_t)n);
+    for (uint32_t q = 0; q < n; ++q) h = splitmix64(h ^ vals[q]);
+    return h;
+}
+
+// The claim word of a row: a mix of the whole tuple, never 0
+__device__ __forceinline__ uint64_t blog_hash(const sga_block_row &k) {
+    uint64_t h = splitmix64((uint64_t)k.time_slot);
+    h = splitmix64(h ^ ((uint64_t)k.origin << 32 | k.resource));
+    h = splitmix64(h ^ ((uint64_t)k.tag_kind << 40 | (uint64_t)k.decision << 32 | k.detail));
+    h = splitmix64(h ^ k.tag);
+    return h ? h : 1ull;
+}
+
+// One lane adds a wave's combined (sum of acquire, entries) to the tuple's row: linear probing from the hash, a
+// free slot claimed by one compare-and-swap (the winner stores the key fields -- never count or events, which
+// others may already be adding to), a slot holding the same hash shared.  No probe waits for anybody; a tuple
+// that finds neither within the probe limit goes to the lost counters.
+__device__ __forceinline__ void blog_update(const BlogTab &tb, const sga_block_row &k, uint64_t h, int64_t sum,
+                                            uint32_t cnt) {
+    const uint32_t limit = min(tb.mask + 1u, kBlogProbe);
+    uint32_t s = (uint32_t)(h >> 20) & tb.mask;
+    for (uint32_t p = 0; p < limit; ++p, s = (s + 1u) & tb.mask) {
+        unsigned long long cur = __atomic_load_n(&tb.hash[s], __ATOMIC_RELAXED);
+        if (cur == 0ull) {
+            cur = atomicCAS(&tb.hash[s], 0ull, (unsigned long long)h);
+            if (cur == 0ull) {
+                sga_block_row &r = tb.row[s];
+                r.time_slot = k.time_slot;
+                r.tag = k.tag;
+                r.resource = k.resource;
+                r.origin = k.origin;
+                r.detail = k.detail;
+                r.decision = k.decision;
+                r.tag_kind = k.tag_kind;
+                atomicAdd(&tb.ctl[2], 1ull);
+                cur = h;
+            }
+        }
+        if (cur == h) {
+            atomicAdd((unsigned long long *)&tb.row[s].count, (unsigned long long)sum);
+            atomicAdd(&tb.row[s].events, cnt);
+            return;
+        }
+    }
+    atomicAdd(&tb.ctl[0], (unsigned long long)cnt);
+    atomicAdd(&tb.ctl[1], (unsigned long long)sum);
+}
+
+// The chunk's last stage when the log is on: one lane an event, grid-stride over whole blocks (every lane of a wave
+// stays in the loop: the combine below is wave-wide).  An entry of the caller's that ended in a BlockException
+// forms its tuple; the parameter tag is args[paramIdx] of the blocking rule, paramIdx as the rule resolved it
+// (ParamRuleDev::idx_res -- set by the check that blocked).  Then the wave combines before touching memory: while
+// a lane holds an unmerged tuple, the first such lane's hash is broadcast and the lanes holding the same one sum
+// their acquire and count themselves -- registers only.  After that loop the first lanes of all the tuples update
+// the table side by side (a loop that updated inside would pay one memory round trip per distinct tuple, in turn).
+// A tuple that at least two lanes share can become the wave's held tuple instead: its sums stay in registers over
+// the wave's later tiles, which merge into it first, and reach the table once, at the end or when a tuple with more
+// lanes in a tile takes its place.  A chunk of blocks on one hot key costs two atomics a wave, not two a lane.
+__global__ __launch_bounds__(kT) void k_blog_add(BlogTab tb, const ResDev *__restrict__ res,
+                                                 const ParamRuleDev *__restrict__ prules, uint32_t nres,
+                                                 const uint8_t *__restrict__ kind_in,
+                                                 const uint32_t *__restrict__ resource,
+                                                 const uint32_t *__restrict__ ts_off, int64_t ts_base,
+                                                 const int32_t *__restrict__ acquire,
+                                                 const uint8_t *__restrict__ flags,
+                                                 const uint64_t *__restrict__ param_in,
+                                                 const uint64_t *__restrict__ pvals,
+                                                 const uint32_t *__restrict__ origin,
+                                                 const int8_t *__restrict__ decision,
+                                                 const int32_t *__restrict__ wait_ms, uint32_t n) {
+    const int lane = (int)(threadIdx.x & 63u);
+    // the held tuple: hash, sums and owner lane are wave-uniform, the key fields stay in lane hl's hk
+    bool held = false;
+    uint64_t hh = 0;
+    int64_t hsum = 0;
+    uint32_t hcnt = 0;
+    int hl = 0;
+    sga_block_row hk{};
+    for (uint32_t i0 = blockIdx.x * kT; i0 < n; i0 += gridDim.x * kT) {
+        const uint32_t i = i0 + threadIdx.x;
+        bool has = false;
+        sga_block_row k{};
+        uint64_t h = 0;
+        if (i < n && kind_in[i] == SGA_KIND_ENTRY) {
+            const int8_t d = decision[i];
+            has = d == SGA_BLOCK_FLOW || d == SGA_BLOCK_PARAM || d == SGA_BLOCK_DEGRADE || d == SGA_BLOCK_SYSTEM ||
+                  d == SGA_BLOCK_AUTHORITY;
+            if (has) {
+                const int64_t t = ts_base + (int64_t)ts_off[i];
+                k.time_slot = t - t % 1000;
+                k.count = (int64_t)acquire[i];
+                k.resource = resource[i];
+                k.origin = origin ? origin[i] : 0u;
+                k.detail = (uint32_t)wait_ms[i];
+                k.decision = (uint8_t)d;
+                if (d == SGA_BLOCK_PARAM && k.resource < nres && k.detail < res[k.resource].n_prules) {
+                    const uint8_t fl = flags[i];
+                    const uint64_t pv = param_in[i];
+                    PArgs pa{nullptr, 0};
+                    if ((fl & SGA_EV_ARGS) && pvals) {
+                        pa.args = pvals + (pv >> 32);
+                        pa.pvals = pvals;
+                        pa.nargs = (uint32_t)pv;
+                    } else if ((fl & SGA_EV_HAS_PARAM) && (fl & SGA_EV_PARAM_LIST) && pvals) {
+                        pa = PArgs{pvals + (pv >> 32), (uint32_t)pv};
+                    }
+                    const int32_t idx = prules[res[k.resource].prule_off + k.detail].idx_res;
+                    if (idx >= 0 && (uint32_t)idx < ev_nargs(pa, (fl & SGA_EV_HAS_PARAM) != 0)) {
+                        const uint64_t *vals;
+                        uint32_t nv;
+                        const int ak = ev_arg(pa, (uint32_t)idx, pv, &vals, &nv);
+                        if (ak == ARG_LIST) {
+                            k.tag = blog_list_tag(vals, nv);
+                            k.tag_kind = kBlogList;
+                        } else if (ak == ARG_SCALAR) {
+                            k.tag = vals[0];
+                        }
+                    }
+                }
+                h = blog_hash(k);
+            }
+        }
+        unsigned long long pend = __ballot(has);
+        uint32_t hm = 0;  // lanes of this tile that merged into the held tuple
+        if (held && pend) {
+            const bool same = has && h == hh;
+            const unsigned long long sm = __ballot(same);
+            if (sm) {
+                hsum += wave_sum_i64(same ? k.count : 0);
+                hm = (uint32_t)__popcll(sm);
+                hcnt += hm;
+                has = has && !same;
+                pend &= ~sm;
+            }
+        }
+        bool first = false;  // this lane is the first of a tuple that goes to the table after the loop
+        int64_t gsum = 0;
+        uint32_t gcnt = 0;
+        while (pend) {
+            const int lead = __ffsll(pend) - 1;
+            const uint64_t lh = (uint64_t)readlane_i64((int64_t)h, lead);
+            const bool same = has && h == lh;
+            const unsigned long long sm = __ballot(same);
+            int64_t sum = k.count;
+            uint32_t cnt = 1;
+            if (sm & (sm - 1ull)) {  // wave-uniform: more than one lane holds the tuple
+                sum = wave_sum_i64(same ? k.count : 0);
+                cnt = (uint32_t)__popcll(sm);
+            }
+            if (cnt >= 2 && cnt > hm) {  // wave-uniform: the tuple becomes the held one, the old one goes out
+                if (held && lane == hl) blog_update(tb, hk, hh, hsum, hcnt);
+                held = true;
+                hh = lh;
+                hsum = sum;
+                hcnt = hm = cnt;
+                hl = lead;
+                if (lane == lead) hk = k;
+            } else if (lane == lead) {
+                first = true;
+                gsum = sum;
+                gcnt = cnt;
+            }
+            has = has && !same;
+            pend &= ~sm;
+        }
+        if (first) blog_update(tb, k, h, gsum, gcnt);
+    }
+    if (held && lane == hl) blog_update(tb, hk, hh, hsum, hcnt);
+}
+
+// Drain, first half: the rows of finished seconds (time_slot <= limit) copied out, counted, nothing removed yet
+__global__ __launch_bounds__(kT) void k_blog_drain(BlogTab tb, uint32_t slots, int64_t limit, sga_block_row *out,
+                                                   uint32_t *count) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= slots || !tb.hash[i]) return;
+    const sga_block_row r = tb.row[i];
+    if (r.time_slot > limit) return;
+    out[atomicAdd(count, 1u)] = r;  // out holds `slots` rows
+}
+
+// Drain, second half: the survivors rehashed into the other (empty) table, which then becomes the live one.  The
+// hashes of one table are distinct, so every survivor claims a slot of its own; the table is as large as the old
+// one, so the probe ends.
+__global__ __launch_bounds__(kT) void k_blog_rebuild(BlogTab from, BlogTab to, uint32_t slots, int64_t limit) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= slots) return;
+    const unsigned long long h = from.hash[i];
+    if (!h) return;
+    const sga_block_row r = from.row[i];
+    if (r.time_slot <= limit) return;
+    uint32_t s = (uint32_t)(h >> 20) & to.mask;
+    for (uint32_t p = 0; p < slots; ++p, s = (s + 1u) & to.mask)
+        if (atomicCAS(&to.hash[s], 0ull, h) == 0ull) {
+            to.row[s] = r;
+            atomicAdd(&to.ctl[2], 1ull);
+            return;
+        }
+}
+
 __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *__restrict__ kind,
                        const uint32_t *__restrict__ resource, const uint32_t *__restrict__ ts_off, int64_t ts_base,
                        const int32_t *__restrict__ acquire, const uint8_t *__restrict__ flags,
@@ -6829,6 +7033,7 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
     std::vector<std::vector<uint8_t>> first(ordered ? nres : 0);  // per rule: a non-default limitApp (sorts first)
     std::vector<std::vector<uint32_t>> plim(ordered ? nres : 0);  // per rule: the limitApp the replay selects by
     std::vector<std::vector<uint32_t>> pctx(ordered ? nres : 0);  // per rule: a CHAIN rule's context, else 0
+    std::vector<std::vector<uint32_t>> pidx(nres);                // per rule: its index in `rules`
     int valid = 0;
     for (size_t i = 0; i < n; ++i) {
         const sga_flow_rule &r = rules[i];
@@ -6885,6 +7090,7 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
             d.slope = (cfg.cold_factor - 1.0) / r.count / (double)(d.max_token - d.warning_token);
         }
         per[r.resource].push_back(d);
+        pidx[r.resource].push_back((uint32_t)i);
         // (an unknown limitApp is stored as "default" on a rule that never applies: its resource needs no replay)
         if (ordered) plim[r.resource].push_back(lim == SGA_LIMIT_UNKNOWN || chain_unknown ? SGA_LIMIT_DEFAULT : lim);
         if (ordered) first[r.resource].push_back(lim != SGA_LIMIT_DEFAULT);
@@ -6900,15 +7106,17 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
         auto rank = [&](size_t k) { return (per[r][k].cluster ? 2 : 0) + (first[r][k] ? 0 : 1); };
         std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return rank(a) < rank(b); });
         std::vector<FlowRuleDev> sorted;
-        std::vector<uint32_t> slim, sctx;
+        std::vector<uint32_t> slim, sctx, sidx;
         for (size_t k : ord) {
             sorted.push_back(per[r][k]);
+            sidx.push_back(pidx[r][k]);
             slim.push_back(plim[r][k]);
             sctx.push_back(pctx[r][k]);
         }
         per[r].swap(sorted);
         plim[r].swap(slim);
         pctx[r].swap(sctx);
+        pidx[r].swap(sidx);
     }
     // RELATE groups: the components of the (resource, refResource) pairs -- a resource whose only RELATE rule
     // names itself is a component of one -- each led by its smallest member.  A group's events are decided in
@@ -6963,6 +7171,8 @@ int FlowEngine::load_flow_rules(const sga_flow_rule *rules, size_t n, const uint
             }
     }
     h_rules.clear();
+    h_flow_idx.clear();
+    for (uint32_t r = 0; r < nres; ++r) h_flow_idx.insert(h_flow_idx.end(), pidx[r].begin(), pidx[r].end());
     has_cluster_rules = false;
     cluster_resolved_gen = ~0ull;
     for (uint32_t r = 0; r < nres; ++r) {
@@ -7059,6 +7269,7 @@ int FlowEngine::load_param_rules(const sga_param_rule *rules, size_t n) {
     }
     std::vector<ParamRuleDev> nr;
     std::vector<sga_param_rule> nsrc;
+    std::vector<uint32_t> nidx;
     std::vector<std::vector<uint64_t>> nhv;
     std::vector<std::vector<int32_t>> nht;
     std::vector<uint64_t> hv;
@@ -7109,6 +7320,7 @@ int FlowEngine::load_param_rules(const sga_param_rule *rules, size_t n) {
             src.hot_values = nullptr;
             src.hot_thresholds = nullptr;
             nsrc.push_back(src);
+            nidx.push_back((uint32_t)i);
             nhv.emplace_back(r.hot_values, r.hot_values + r.n_hot);
             nht.emplace_back(r.hot_thresholds, r.hot_thresholds + r.n_hot);
             valid++;
@@ -7139,6 +7351,7 @@ int FlowEngine::load_param_rules(const sga_param_rule *rules, size_t n) {
     for (const ParamRuleDev &d : nr) has_cluster_prules |= d.cluster != 0;
     h_prules = nr;
     h_prule_src = nsrc;
+    h_prule_idx = nidx;
     h_prule_hot_v = nhv;
     h_prule_hot_t = nht;
     d_prules.alloc(std::max<size_t>(nr.size(), 1));
@@ -7174,6 +7387,7 @@ int FlowEngine::load_degrade_rules(const sga_degrade_rule *rules, size_t n) {
     }
     std::vector<CbDev> nc;
     std::vector<sga_degrade_rule> nsrc;
+    std::vector<uint32_t> nidx;
     std::vector<bool> used(h_cb_src.size(), false);
     int valid = 0;
     for (uint32_t res = 0; res < nres; ++res) {
@@ -7220,6 +7434,7 @@ int FlowEngine::load_degrade_rules(const sga_degrade_rule *rules, size_t n) {
             }
             nc.push_back(d);
             nsrc.push_back(r);
+            nidx.push_back((uint32_t)i);
             cnt++;
             valid++;
         }
@@ -7227,6 +7442,7 @@ int FlowEngine::load_degrade_rules(const sga_degrade_rule *rules, size_t n) {
     }
     h_cbs = nc;
     h_cb_src = nsrc;
+    h_cb_idx = nidx;
     d_cbs.alloc(std::max<size_t>(nc.size(), 1));
     if (!nc.empty())
         SGA_HIP_CHECK(hipMemcpyAsync(d_cbs.p, nc.data(), nc.size() * sizeof(CbDev), hipMemcpyHostToDevice, stream));
@@ -7665,6 +7881,7 @@ int FlowEngine::submit_small(Chunk c, const uint8_t *kind, const uint32_t *resou
                        lru_counts() ? 0 : 1);
     SGA_HIP_CHECK(hipGetLastError());
     chunk_epilogue(c, true);
+    block_log_pass(c);
     SGA_HIP_CHECK(hipStreamSynchronize(c.s));
     std::memcpy(decision, h + o_dec, m);
     if (wait_ms) std::memcpy(wait_ms, h + o_wait, 4 * m);
@@ -7875,6 +8092,7 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                 if (seq_lane) chunk_seq(c);
                 else chunk_pipeline(c, has_in);
                 chunk_epilogue(c, false);
+                block_log_pass(c);
                 SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
                 if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
                 uint32_t ovf = 0;
@@ -7978,6 +8196,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     hipLaunchKernelGGL(k_lfail, dim3(gb), dim3(kT), 0, s, d_gate.p, d_overflow.p, d_gate.p + 1, c.m, c.decision,
                        c.wait_ms);
     SGA_HIP_CHECK(hipGetLastError());
+    block_log_pass(c);  // after k_lfail: a refused chunk answers -1 and logs nothing
     seq += n;
     return 0;
 }
@@ -8478,6 +8697,113 @@ int FlowEngine::authority_check(const uint32_t *resource, const uint32_t *origin
         SGA_HIP_CHECK(hipStreamSynchronize(stream));
         for (size_t i = 0; i < m; ++i) pass[b + i] ^= 1;  // turned -> pass
     }
+    return 0;
+}
+
+// ---- block log
+int FlowEngine::block_log_enable(uint32_t max_rows) {
+    if (!nres) return SGA_EINVAL;
+    if (max_rows == 0) max_rows = 1u << 16;  // the default: a choice, not a measurement
+    if (max_rows > (1u << 26)) return SGA_EINVAL;
+    uint32_t slots = 64;
+    while (slots < max_rows) slots <<= 1;
+    if (blog.on) {  // an empty log may be resized
+        unsigned long long used = 0;
+        SGA_HIP_CHECK(hipMemcpyAsync(&used, blog.ctl.p + 2, 8, hipMemcpyDeviceToHost, stream));
+        SGA_HIP_CHECK(hipStreamSynchronize(stream));
+        if (used) return SGA_EINVAL;
+        if (slots == blog.slots) return 0;
+    }
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    for (int k = 0; k < 2; ++k) {
+        blog.hash[k].alloc(slots);
+        blog.row[k].alloc(slots);
+        SGA_HIP_CHECK(hipMemsetAsync(blog.hash[k].p, 0, blog.hash[k].bytes(), stream));
+        SGA_HIP_CHECK(hipMemsetAsync(blog.row[k].p, 0, blog.row[k].bytes(), stream));
+    }
+    blog.out.alloc(slots);
+    if (!blog.ctl.p) {
+        blog.ctl.alloc(4);
+        blog.cnt.alloc(1);
+        SGA_HIP_CHECK(hipMemsetAsync(blog.ctl.p, 0, blog.ctl.bytes(), stream));
+    }
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    blog.slots = slots;
+    blog.live = 0;
+    blog.on = true;
+    return 0;
+}
+
+// The last stage of a chunk on every entry, on the chunk's stream: after chunk_epilogue on the host entries, after
+// k_lfail on the device entry.  Nothing when the log is off.
+void FlowEngine::block_log_pass(const Chunk &c) {
+    if (!blog.on) return;
+    // four tiles a block and at most 512 blocks: a wave's held tuple gathers what its tiles share
+    const uint32_t nb = std::min<uint32_t>((c.m + 4 * kT - 1) / (4 * kT), 512);
+    hipLaunchKernelGGL(k_blog_add, dim3(nb), dim3(kT), 0, c.s, blog_tab(blog.live), d_res.p, d_prules.p, nres, c.kind_in,
+                       c.resource, c.ts_off, c.ts_base, c.acquire, c.flags, c.param, c.pvals, c.ids[kPairOrigin],
+                       c.decision, c.wait_ms, c.m);
+    SGA_HIP_CHECK(hipGetLastError());
+}
+
+int FlowEngine::block_log_drain(int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n, uint64_t *lost_events,
+                                int64_t *lost_count) {
+    if (!blog.on || !n || (cap && !rows)) return SGA_EINVAL;
+    *n = 0;
+    const int64_t limit = before_ms < 1000 ? -1 : before_ms - 1000;  // due: time_slot + 1000 <= before_ms
+    const uint32_t slots = blog.slots, nb = (slots + kT - 1) / kT;
+    const BlogTab live = blog_tab(blog.live), other = blog_tab(blog.live ^ 1);
+    SGA_HIP_CHECK(hipMemsetAsync(blog.cnt.p, 0, 4, stream));
+    hipLaunchKernelGGL(k_blog_drain, dim3(nb), dim3(kT), 0, stream, live, slots, limit, blog.out.p, blog.cnt.p);
+    SGA_HIP_CHECK(hipGetLastError());
+    uint32_t cnt = 0;
+    unsigned long long ctl[3] = {0, 0, 0};
+    SGA_HIP_CHECK(hipMemcpyAsync(&cnt, blog.cnt.p, 4, hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipMemcpyAsync(ctl, blog.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    *n = cnt;
+    if (cnt > cap) return SGA_ERANGE;  // nothing removed, the lost counters kept
+    if (cnt) {
+        SGA_HIP_CHECK(hipMemcpyAsync(rows, blog.out.p, (size_t)cnt * sizeof(sga_block_row), hipMemcpyDeviceToHost, stream));
+        // the survivors move to the other table (empty: zeroed when it was left), which becomes the live one
+        SGA_HIP_CHECK(hipMemsetAsync(blog.ctl.p + 2, 0, 8, stream));
+        if (cnt < ctl[2]) {
+            hipLaunchKernelGGL(k_blog_rebuild, dim3(nb), dim3(kT), 0, stream, live, other, slots, limit);
+            SGA_HIP_CHECK(hipGetLastError());
+            blog.live ^= 1;
+        }
+        SGA_HIP_CHECK(hipMemsetAsync(live.hash, 0, (size_t)slots * 8, stream));
+        SGA_HIP_CHECK(hipMemsetAsync(live.row, 0, (size_t)slots * sizeof(sga_block_row), stream));
+    }
+    if (ctl[0] || ctl[1]) SGA_HIP_CHECK(hipMemsetAsync(blog.ctl.p, 0, 16, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (lost_events) *lost_events = ctl[0];
+    if (lost_count) *lost_count = (int64_t)ctl[1];
+    std::sort(rows, rows + cnt, [](const sga_block_row &x, const sga_block_row &y) {
+        if (x.time_slot != y.time_slot) return x.time_slot < y.time_slot;
+        if (x.resource != y.resource) return x.resource < y.resource;
+        if (x.decision != y.decision) return x.decision < y.decision;
+        if (x.detail != y.detail) return x.detail < y.detail;
+        if (x.origin != y.origin) return x.origin < y.origin;
+        if (x.tag_kind != y.tag_kind) return x.tag_kind < y.tag_kind;
+        return x.tag < y.tag;
+    });
+    return 0;
+}
+
+int FlowEngine::block_rule_index(int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index) const {
+    if (!index || resource >= nres || resource >= h_res.size()) return SGA_EINVAL;
+    const ResDev &R = h_res[resource];
+    const std::vector<uint32_t> *idx;
+    uint32_t off, cnt;
+    switch (decision) {
+    case SGA_BLOCK_FLOW: idx = &h_flow_idx, off = R.rule_off, cnt = R.n_rules; break;
+    case SGA_BLOCK_PARAM: idx = &h_prule_idx, off = R.prule_off, cnt = R.n_prules; break;
+    case SGA_BLOCK_DEGRADE: idx = &h_cb_idx, off = R.cb_off, cnt = R.n_cbs; break;
+    default: return SGA_EINVAL;
+    }
+    if (detail >= cnt || (size_t)off + detail >= idx->size()) return SGA_EINVAL;
+    *index = (*idx)[off + detail];
     return 0;
 }
 

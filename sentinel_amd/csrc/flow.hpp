@@ -197,6 +197,20 @@ struct AuthState {
     uint32_t nres;
 };
 
+// Block log (LogSlot, sga_block_log_enable): an open-addressing table of sga_block_row in HBM, one row per
+// (time_slot, resource, decision, detail, origin, tag_kind, tag).  hash[s] is the slot's claim word -- a 64-bit mix
+// of the whole tuple, never 0 (0: empty) -- and the only thing a lookup compares: tuples whose hashes collide
+// share a row.  A slot is claimed by one compare-and-swap; the winner stores the key fields, everybody adds count
+// and events with integer atomics, and nobody ever waits for another wave.
+struct BlogTab {
+    unsigned long long *hash;
+    sga_block_row *row;
+    unsigned long long *ctl;  // [0] lost_events [1] lost_count [2] rows claimed in the live table
+    uint32_t mask;
+};
+constexpr uint32_t kBlogProbe = 128;  // linear probes before a tuple counts as lost
+constexpr uint8_t kBlogScalar = 0, kBlogList = 1;  // sga_block_row::tag_kind
+
 struct FlowState {
     int64_t *node;
     FlowRuleDev *rules;
@@ -540,6 +554,27 @@ struct FlowEngine {
     // sets c.kind: the chunk's effective kind (c.kind_in when no rule is on the device or it has no origin array)
     void authority_pass(Chunk &c);
     void authority_answer(const Chunk &c);
+    // Block log (BlogTab): off until block_log_enable -- no chunk launches or allocates anything for it before.
+    // Two tables: a drain moves the rows of finished seconds out and rehashes the survivors into the other one
+    // (deleting in place would break probe chains).  block_log_pass is the chunk's last stage on every entry.
+    struct BlockLog {
+        bool on = false;
+        uint32_t slots = 0;
+        int live = 0;
+        DevBuf<unsigned long long> hash[2], ctl;
+        DevBuf<sga_block_row> row[2], out;
+        DevBuf<uint32_t> cnt;
+    } blog;
+    BlogTab blog_tab(int which) const {
+        return BlogTab{blog.hash[which].p, blog.row[which].p, blog.ctl.p, blog.slots - 1};
+    }
+    int block_log_enable(uint32_t max_rows);
+    void block_log_pass(const Chunk &c);
+    int block_log_drain(int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n, uint64_t *lost_events,
+                        int64_t *lost_count);
+    // per rule in device order (FlowState::rules / prules / cbs): its index in the array the loader was given
+    std::vector<uint32_t> h_flow_idx, h_prule_idx, h_cb_idx;
+    int block_rule_index(int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index) const;
     SysDev sys{0, 0, 0, 0, 1.7976931348623157e308, 1.7976931348623157e308, 1.7976931348623157e308, INT64_MAX,
                INT64_MAX, -1.0, -1.0};
     DevBuf<sga_metric_node> d_metrics;

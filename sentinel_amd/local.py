@@ -67,9 +67,15 @@ KIND_EXIT = 1
 
 
 class BlockException(Exception):
-    def __init__(self, resource: str):
+    """rule: the loaded rule object that blocked (None for a SystemBlockException, and while the rule's manager
+    has not loaded through this sentinel); rule_limit_app: BlockException.getRuleLimitApp() as each subclass's
+    constructor sets it -- what LogSlot writes into sentinel-block.log."""
+
+    def __init__(self, resource: str, rule=None, rule_limit_app: str = RuleConstant.LIMIT_APP_DEFAULT):
         super().__init__(resource)
         self.resource = resource
+        self.rule = rule
+        self.rule_limit_app = rule_limit_app
 
 
 class FlowException(BlockException):
@@ -265,7 +271,7 @@ class LocalSentinel:
 
     def __init__(self, engine: Engine, resources: Sequence[str], origins: Optional[Sequence[str]] = None,
                  max_origin_nodes: int = 0, contexts: Optional[Sequence[str]] = None, max_context_nodes: int = 0,
-                 tree: bool = False):
+                 tree: bool = False, block_log=False):
         """origins: the caller names events may carry (ContextUtil.enter's origin), registered up front like
         the resources; None = no origin tracking.  max_origin_nodes sizes the engine's table of (resource,
         origin) nodes (0: the engine's default).  contexts: the context names events may carry
@@ -274,7 +280,9 @@ class LocalSentinel:
         submit, submit_device and entry take `parent`, the enclosing entry, and each DefaultNode keeps the parent
         of its first entry (NodeSelectorSlot's addChild); tree_rows and invocation_tree read the result.  The
         default context (sentinel_default_context) appears in the tree only if the caller registers that name and
-        submits its entries with that id: context 0 stays untracked."""
+        submits its entries with that id: context 0 stays untracked.  block_log: True (the engine's default of 65,536
+        rows) or a row count turns on the engine's block log (LogSlot: sga_block_log_enable); block_rows drains it
+        and block_log.BlockLogWriter writes sentinel-block.log from it."""
         self.engine = engine
         if tree and not contexts:
             raise ValueError("tree=True needs registered contexts")
@@ -310,6 +318,16 @@ class LocalSentinel:
         if self.contexts:
             check(_lib.load().sga_flow_set_contexts(engine.handle, len(self.contexts), max_context_nodes),
                   engine.handle, "setContexts")
+        # what the rule managers last sent to the engine, by decision code: a list in the order of the array the
+        # loader was given (sga_block_rule_index answers an index into it); AuthorityRules by resource id
+        self._loaded: Dict[int, object] = {}
+        # String.valueOf(args[paramIdx]) of the parameter blocks entry() raised, by (tag, tag_kind): bounded
+        self.param_texts: Dict[tuple, str] = {}
+        self.block_log_rows = 0
+        if block_log:
+            rows = 0 if block_log is True else int(block_log)
+            check(_lib.load().sga_block_log_enable(engine.handle, rows), engine.handle, "blockLogEnable")
+            self.block_log_rows = max(64, 1 << (rows - 1).bit_length()) if rows else 1 << 16
 
     def context_id(self, name: str) -> int:
         """Dense id of a registered context; "" is 0 (no tracked context)."""
@@ -527,10 +545,74 @@ class LocalSentinel:
                                 context=[self.context_id(context)] if context else None, parent=pa)
         d = int(dec[0])
         if d in _EXC:
-            raise _EXC[d](resource)
+            raise self._block_exception(d, resource, rid, int(wait[0]), tuple(args), origin)
         param = param_value(args[0]) if len(args) > 0 and args[0] is not None and \
             not isinstance(args[0], (list, tuple)) else None
         return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin, context, parent)
+
+    # ---- block attribution (LogSlot)
+    _PARAM_TEXTS_MAX = 4096
+
+    def block_rule_index(self, decision: int, resource, detail: int) -> int:
+        """sga_block_rule_index: the position, in the array the matching loader was last given, of the rule a FLOW /
+        PARAM / DEGRADE block detail names (the _origin / _ctx flow loaders reorder as FlowRuleComparator does)."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        idx = C.c_uint32()
+        check(_lib.load().sga_block_rule_index(self.engine.handle, int(decision), rid, int(detail), C.byref(idx)),
+              self.engine.handle, "blockRuleIndex")
+        return int(idx.value)
+
+    def block_rule(self, decision: int, resource, detail: int):
+        """The loaded rule object a block names: the FlowRule / ParamFlowRule / DegradeRule at block_rule_index, the
+        resource's AuthorityRule, None for a system block or while the manager has not loaded through this sentinel."""
+        rid = resource if isinstance(resource, int) else self.ids[resource]
+        loaded = self._loaded.get(int(decision))
+        if decision == Decision.BLOCK_AUTHORITY:
+            return None if loaded is None else loaded.get(rid)
+        if loaded is None or decision == Decision.BLOCK_SYSTEM:
+            return None
+        return loaded[self.block_rule_index(decision, rid, detail)]
+
+    def _block_exception(self, d: int, resource: str, rid: int, detail: int, args: tuple, origin: str):
+        from . import block_log as BL
+        rule = self.block_rule(d, rid, detail)
+        if d == Decision.BLOCK_SYSTEM:  # SystemBlockException(resourceName, limitType)
+            lim = BL.SYSTEM_LIMIT_TYPE[detail] if detail < len(BL.SYSTEM_LIMIT_TYPE) else str(detail)
+        elif d == Decision.BLOCK_AUTHORITY:  # AuthorityException(context.getOrigin(), rule)
+            lim = origin
+        elif d == Decision.BLOCK_PARAM:  # ParamFlowException(resourceName, String.valueOf(args[paramIdx]), rule)
+            # a negative paramIdx counts from the end (ParamFlowSlot.applyRealParamIdx, fixed on the rule at its
+            # first check; resolved here against this call's args)
+            idx = getattr(rule, "param_idx", 0)
+            if idx < 0:
+                idx = len(args) + idx if -idx <= len(args) else -idx
+            arg = args[idx] if 0 <= idx < len(args) else None
+            lim = BL.java_text(arg)
+            if arg is not None:
+                if isinstance(arg, (list, tuple)):
+                    key = (BL.list_tag([param_value(x) for x in arg]), BL.TAG_LIST)
+                else:
+                    key = (param_value(arg), BL.TAG_SCALAR)
+                if key not in self.param_texts and len(self.param_texts) >= self._PARAM_TEXTS_MAX:
+                    self.param_texts.pop(next(iter(self.param_texts)))  # the oldest text goes
+                self.param_texts[key] = lim
+        else:  # FlowException(rule.getLimitApp(), rule), DegradeException(rule.getLimitApp(), rule)
+            lim = getattr(rule, "limit_app", None) or RuleConstant.LIMIT_APP_DEFAULT
+        return _EXC[d](resource, rule, lim)
+
+    def block_rows(self, before_ms: Optional[int] = None):
+        """sga_block_log_drain: (rows, lost_events, lost_count).  rows: a block_log.BLOCK_ROW_DTYPE array of the
+        aggregated keys whose second is finished at before_ms (None: every row), sorted by (time_slot, resource,
+        decision, detail, origin, tag_kind, tag); the lost counters: entries, and their acquire sum, that found no
+        room in the table since the last drain."""
+        from .block_log import BLOCK_ROW_DTYPE
+        before = (1 << 63) - 1 if before_ms is None else int(before_ms)
+        cap = self.block_log_rows
+        n, le, lc = C.c_size_t(), C.c_uint64(), C.c_int64()
+        out = np.zeros(max(1, cap), dtype=BLOCK_ROW_DTYPE)
+        check(_lib.load().sga_block_log_drain(self.engine.handle, before, out.ctypes.data, cap, C.byref(n),
+                                              C.byref(le), C.byref(lc)), self.engine.handle, "blockLogDrain")
+        return out[:n.value].copy(), int(le.value), int(lc.value)
 
     def node(self, resource, now: int) -> NodeView:
         """ClusterNode views; resource ENTRY_NODE (or TOTAL_IN_RESOURCE_NAME) is Constants.ENTRY_NODE."""
@@ -809,6 +891,8 @@ class FlowRuleManager:
                 a.cluster_sample_count = 0 if cc is None else cc.sample_count
                 a.cluster_window_ms = 0 if cc is None else cc.window_interval_ms
                 a.cluster_strategy = 0 if cc is None else cc.strategy
+        if hasattr(self.s, "_loaded"):
+            self.s._loaded[Decision.BLOCK_FLOW] = rules
         if cids:
             return check(_lib.load().sga_load_flow_rules_ctx(self.s.engine.handle, arr, lim if oids else None,
                                                              len(rules)),
@@ -863,6 +947,8 @@ class ParamFlowRuleManager:
             a.hot_values = C.cast(hv, C.POINTER(C.c_uint64))
             a.hot_thresholds = C.cast(ht, C.POINTER(C.c_int32))
         rc = _lib.load().sga_load_param_rules(self.s.engine.handle, arr, len(rules))
+        if hasattr(self.s, "_loaded"):
+            self.s._loaded[Decision.BLOCK_PARAM] = rules
         self._keep = keep
         return check(rc, self.s.engine.handle, "ParamFlowRuleManager.loadRules")
 
@@ -889,6 +975,8 @@ class DegradeRuleManager:
             a.min_request_amount = r.min_request_amount
             a.slow_ratio_threshold = r.slow_ratio_threshold
             a.stat_interval_ms = r.stat_interval_ms
+        if hasattr(self.s, "_loaded"):
+            self.s._loaded[Decision.BLOCK_DEGRADE] = rules
         return check(_lib.load().sga_load_degrade_rules(self.s.engine.handle, arr, len(rules)), self.s.engine.handle,
                      "DegradeRuleManager.loadRules")
 
@@ -941,6 +1029,8 @@ class AuthorityRuleManager:
                                                    off.ctypes.data, len(send), idv.ctypes.data),
               self.s.engine.handle, "AuthorityRuleManager.loadRules")
         self._kept = kept
+        if hasattr(self.s, "_loaded"):
+            self.s._loaded[Decision.BLOCK_AUTHORITY] = {self.s.ids[r.resource]: r for r in send}
         return len(kept)
 
 
