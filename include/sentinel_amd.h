@@ -855,6 +855,38 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
  * resource's rules: SGA_EINVAL. */
 int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index);
 
+/* ---- circuit breaker events (EventObserverRegistry; new entry points only) ---- */
+/* AbstractCircuitBreaker notifies every CircuitBreakerStateChangeObserver of each transition with (prevState,
+ * newState, rule, snapshotValue) (CORE/slots/block/degrade/circuitbreaker/AbstractCircuitBreaker.java:102-164).
+ * Once enabled, the kernels that decide a breaker append one record per transition to an engine-resident buffer,
+ * on every submit entry (host and device, _origin, _ctx, _tree, the sga_event_* queue).  Off by default: an engine
+ * that never enables the log launches and allocates nothing for it. */
+#define SGA_CB_CLOSED 0u
+#define SGA_CB_OPEN 1u
+#define SGA_CB_HALF_OPEN 2u
+typedef struct sga_cb_event {
+    int64_t ts;        /* time of the event that caused the transition */
+    double value;      /* snapshotValue when next is SGA_CB_OPEN (the reference passes null otherwise), else 0 */
+    uint64_t seq;      /* events submitted to the engine since the log was enabled and before this one */
+    uint32_t resource; /* dense resource id */
+    uint32_t breaker;  /* index k in DegradeRuleManager list order (as sga_circuit_breaker_state) */
+    uint32_t epoch;    /* sga_load_degrade_rules calls so far: the rule list k indexes */
+    uint16_t sub;      /* emission order within one event */
+    uint8_t prev, next; /* SGA_CB_*; sizeof == 40 */
+} sga_cb_event;
+
+/* Turns the log on with room for max_events records (0: the default of 65,536; at least 64; rounded up to a power
+ * of two); seq counts from the first call.  Calling it again resizes an empty log; with records pending:
+ * SGA_EINVAL.  Also SGA_EINVAL: an engine without resources (sga_flow_set_resources comes first), and max_events
+ * above 2^26.  A transition that finds the buffer full is counted as lost and changes no breaker. */
+int sga_cb_events_enable(sga_engine *e, uint32_t max_events);
+
+/* Moves out every pending record, sorted by (seq, sub): the order in which the reference would have called the
+ * observers; *n = their number.  More than cap: SGA_ERANGE, *n = the number needed, nothing removed, lost neither
+ * returned nor cleared.  *lost (may be NULL): transitions that found no room since the last successful drain --
+ * returned and cleared.  Waits for the engine stream.  An engine without the log: SGA_EINVAL. */
+int sga_cb_events_drain(sga_engine *e, sga_cb_event *ev, size_t cap, size_t *n, uint64_t *lost);
+
 /* SystemRule (CORE/slots/system/SystemRule.java:43-50); negative = not set. */
 typedef struct sga_system_rule {
     double highest_system_load;

@@ -120,6 +120,12 @@ class SgaBlockRow(C.Structure):  # sga_block_row: one aggregated key of the bloc
                 ("tag_kind", C.c_uint8), ("reserved", C.c_uint8 * 6)]
 
 
+class SgaCbEvent(C.Structure):  # sga_cb_event: one circuit breaker transition
+    _fields_ = [("ts", C.c_int64), ("value", C.c_double), ("seq", C.c_uint64), ("resource", C.c_uint32),
+                ("breaker", C.c_uint32), ("epoch", C.c_uint32), ("sub", C.c_uint16), ("prev", C.c_uint8),
+                ("next", C.c_uint8)]
+
+
 SGA_TAG_SCALAR, SGA_TAG_LIST = 0, 1  # sga_block_row.tag_kind
 
 SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
@@ -256,6 +262,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "sga_block_rule_index": (C.c_int, [C.c_void_p, C.c_int8, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sga_cb_events_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "sga_cb_events_drain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_uint64)]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_wire_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(SgaWireBatch)]),

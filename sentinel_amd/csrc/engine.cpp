@@ -2680,6 +2680,20 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
     });
 }
 
+int sga_cb_events_enable(sga_engine *e, uint32_t max_events) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.cb_events_enable(max_events);
+    });
+}
+
+int sga_cb_events_drain(sga_engine *e, sga_cb_event *ev, size_t cap, size_t *n, uint64_t *lost) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.cb_events_drain(ev, cap, n, lost);
+    });
+}
+
 int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index) {
     return guarded(e, [&](Engine &g) { return g.flow.block_rule_index(decision, resource, detail, index); });
 }

@@ -673,7 +673,13 @@ __device__ void cb_stat_at(CbDev &b, int64_t ws) {  // LeapArray(1, statInterval
 
 // DegradeSlot.entry over the resource's breakers (DegradeSlot.java:52-66): tryPass of each in order;
 // a breaker moved to HALF_OPEN goes back to OPEN when a later one blocks (whenTerminate, blockError)
-__device__ int degrade_block_index(CbDev *cbs, uint32_t n, int64_t t) {  // -1: every breaker passes
+// kb: the breaker that blocks, -1: every breaker passes; moved (breaker events): the breakers this entry took to
+// HALF_OPEN, as a mask -- returned by value: an out-parameter of a function that is not inlined lives in scratch
+struct DegradeRes {
+    int kb;
+    uint64_t moved;
+};
+__device__ DegradeRes degrade_check(CbDev *cbs, uint32_t n, int64_t t) {
     uint64_t half_mask = 0;
     for (uint32_t k = 0; k < n; ++k) {
         CbDev &b = cbs[k];
@@ -690,13 +696,10 @@ __device__ int degrade_block_index(CbDev *cbs, uint32_t n, int64_t t) {  // -1: 
                 CbDev &bq = cbs[q];
                 if (((half_mask >> q) & 1) && bq.state == 2) bq.state = 1;
             }
-            return (int)k;
+            return DegradeRes{(int)k, half_mask};
         }
     }
-    return -1;
-}
-__device__ __forceinline__ bool degrade_pass(CbDev *cbs, uint32_t n, int64_t t) {
-    return degrade_block_index(cbs, n, t) < 0;
+    return DegradeRes{-1, half_mask};
 }
 
 // handleStateChangeWhenThresholdExceeded of a CLOSED breaker over its current window's counts
@@ -746,6 +749,66 @@ __device__ void cb_on_complete_ws(CbDev &b, int64_t t, int64_t ws, int64_t rt, b
 
 __device__ __forceinline__ void cb_on_complete(CbDev &b, int64_t t, int64_t rt, bool error) {
     cb_on_complete_ws(b, t, t - t % b.stat_interval, rt, error);
+}
+
+// ---- breaker events (CbLog).  One record per transition, appended by whoever writes CbDev::state; every caller
+// tests FlowState::cbl first, so nothing of this runs while the log is off.
+// seq: the event's number (FlowState::cbl_seq + its index in the chunk); st: prev | next << 8.
+__device__ __noinline__ void cb_emit(const CbLog *lp, uint64_t seq, int64_t t, double value, uint32_t r, uint32_t k,
+                                     uint32_t sub, uint32_t st) {
+    const CbLog log = *lp;
+    const unsigned long long slot = atomicAdd(&log.ctl[0], 1ull);
+    if (slot >= log.cap) {  // full: the transition is counted, the breaker is none the wiser
+        atomicAdd(&log.ctl[1], 1ull);
+        return;
+    }
+    sga_cb_event e;
+    e.ts = t;
+    e.value = value;
+    e.seq = seq;
+    e.resource = r;
+    e.breaker = k;
+    e.epoch = log.epoch;
+    e.sub = (uint16_t)sub;
+    e.prev = (uint8_t)(st & 0xFFu);
+    e.next = (uint8_t)(st >> 8);
+    log.rec[slot] = e;
+}
+// snapshotValue of a CLOSED -> OPEN trip: the figure cb_trips compared (ExceptionCircuitBreaker.java:75-94,
+// ResponseTimeCircuitBreaker.java:88-106)
+__device__ __forceinline__ double cb_snapshot(const CbDev &b, int64_t badc, int64_t total) {
+    return b.grade == 2 ? (double)badc : (double)badc * 1.0 / (double)total;
+}
+// what one onRequestComplete did to the breaker (prev: its state before): HALF_OPEN -> OPEN carries 1.0, a trip the
+// current window's counts (the ones cb_on_complete_ws read: the trip itself leaves the window alone)
+__device__ __forceinline__ void cb_emit_complete(const CbLog *log, uint64_t seq, const CbDev &b, int prev, int64_t t,
+                                                 uint32_t r, uint32_t k, uint32_t sub) {
+    if (b.state == prev) return;
+    double v = 0.0;
+    if (b.state == 1) {
+        if (prev == 2) v = 1.0;
+        else if (b.st_start != kAbsent && !(t - b.st_start > b.stat_interval)) v = cb_snapshot(b, b.st_bad, b.st_total);
+        else v = cb_snapshot(b, 0, 0);
+    }
+    cb_emit(log, seq, t, v, r, k, sub, (uint32_t)prev | (uint32_t)b.state << 8);
+}
+// DegradeSlot.entry's transitions after degrade_check (moved: the breakers it took to HALF_OPEN; kb: the one
+// that blocked, -1 none): every OPEN -> HALF_OPEN in breaker order, then -- the whenTerminate hooks run after the
+// block -- the fall-backs HALF_OPEN -> OPEN (1.0) of the probes before kb
+// A probe of a breaker past the mask's 64 bits (cbs / n given: chain_entry; k_lheavy's LDS copy holds at most
+// kHeavyCbs) is told by its state: HALF_OPEN with this entry's time ahead of the blocking breaker can only be this
+// entry's doing -- one left HALF_OPEN by an earlier entry of the same time would have blocked this one itself.  Such
+// a probe has no fall-back (degrade_check's loop stops at 64), so none is reported.
+__device__ __forceinline__ void cb_emit_entry(const CbLog *log, uint64_t seq, uint64_t moved, int kb, int64_t t,
+                                              uint32_t r, const CbDev *cbs = nullptr, uint32_t n = 0) {
+    uint32_t sub = 0;
+    for (uint64_t m = moved; m; m &= m - 1)
+        cb_emit(log, seq, t, 0.0, r, (uint32_t)__ffsll((unsigned long long)m) - 1, sub++, 1u | 2u << 8);
+    for (uint32_t k = 64; k < (kb < 0 ? n : (uint32_t)kb); ++k)
+        if (cbs[k].state == 2 && cbs[k].probe_t == t) cb_emit(log, seq, t, 0.0, r, k, sub++, 1u | 2u << 8);
+    if (kb < 0) return;
+    for (uint64_t m = kb < 64 ? moved & ((1ull << kb) - 1) : moved; m; m &= m - 1)
+        cb_emit(log, seq, t, 1.0, r, (uint32_t)__ffsll((unsigned long long)m) - 1, sub++, 2u | 1u << 8);
 }
 
 // ------------------------------------------------------------------ slot chain (one event)
@@ -1103,7 +1166,10 @@ __device__ int8_t chain_entry(const Ctx &c, uint32_t r, const ResMem &m, int64_t
         total_wait += w;
     }
     // DegradeSlot
-    if (const int kb = degrade_block_index(m.cbs, R.n_cbs, t); kb >= 0) {
+    const DegradeRes dr = degrade_check(m.cbs, R.n_cbs, t);
+    if ((dr.moved || R.n_cbs > 64) && c.st.cbl)
+        cb_emit_entry(c.st.cbl, c.st.cbl_seq + eidx, dr.moved, dr.kb, t, r, m.cbs, R.n_cbs);
+    if (const int kb = dr.kb; kb >= 0) {
         node_add(c, node, t, MB_BLOCK, acquire);
         *wait_ms = kb;  // block detail: the breaker's index (DegradeRuleManager list order)
         return D_BLOCK_DEGRADE;
@@ -1124,7 +1190,17 @@ __device__ void chain_exit(const Ctx &c, uint32_t r, const ResMem &m, int64_t t,
     node[kNodeThreads] -= 1;
     if (error) node_add(c, node, t, MB_EXC, count);
     param_threads<kLru>(c, r, pa, has_param, param, -1, eidx);  // ParameterMetric.decreaseThreadCount
-    for (uint32_t k = 0; k < R.n_cbs; ++k) cb_on_complete(m.cbs[k], t, rt, error);
+    if (R.n_cbs == 0) return;
+    if (!c.st.cbl) {
+        for (uint32_t k = 0; k < R.n_cbs; ++k) cb_on_complete(m.cbs[k], t, rt, error);
+        return;
+    }
+    uint32_t sub = 0;  // breaker events: the same, each breaker's state compared across its call
+    for (uint32_t k = 0; k < R.n_cbs; ++k) {
+        const int prev = m.cbs[k].state;
+        cb_on_complete(m.cbs[k], t, rt, error);
+        if (m.cbs[k].state != prev) cb_emit_complete(c.st.cbl, c.st.cbl_seq + eidx, m.cbs[k], prev, t, r, k, sub++);
+    }
 }
 
 // eidx: the event's index in the batch (CacheMap access stamps)
@@ -1163,8 +1239,12 @@ __device__ void revoke_event(const Ctx &c, uint32_t r, int64_t t, int a, const P
     node_add(c, nd, t, MB_BLOCK, a);
     param_threads<kLru>(c, r, pa, hp, pv, -1, eidx);
     CbDev *cbs = c.st.cbs + c.st.res[r].cb_off;
+    uint32_t sub = 0;
     for (uint32_t k = 0; k < c.st.res[r].n_cbs; ++k)
-        if (cbs[k].state == 2 && cbs[k].probe_t == t) cbs[k].state = 1;
+        if (cbs[k].state == 2 && cbs[k].probe_t == t) {
+            cbs[k].state = 1;
+            if (c.st.cbl) cb_emit(c.st.cbl, c.st.cbl_seq + eidx, t, 1.0, r, k, sub++, 2u | 1u << 8);
+        }
 }
 
 // ------------------------------------------------------------------ SystemSlot / ENTRY_NODE
@@ -3607,6 +3687,9 @@ __global__ __launch_bounds__(64) void k_lheavy(FlowState st, int64_t max_rt, Flo
     __shared__ int32_t s_pidx;                // the parameter rule's index in force (applyRealParamIdx)
     __shared__ uint64_t s_tmask;              // the resource's thread-count maps
     const Ctx c{st, max_rt, nullptr, 0, 0, nullptr};
+    // breaker events: read once -- st sits behind c's reference, and lane 0's loop would reload it per event
+    const CbLog *const cbl = st.cbl;
+    const uint64_t cbl_seq = st.cbl_seq;
     constexpr uint64_t kLEmpty = ~0ull;  // a value equal to it bypasses the cache (map path)
     constexpr uint32_t kGiNone = 0xFFFFFFFFu, kGiFail = 0xFFFFFFFEu;
     for (int k = threadIdx.x; k < kHeavySlots; k += 64) lval[k] = kLEmpty;
@@ -4063,17 +4146,42 @@ __global__ __launch_bounds__(64) void k_lheavy(FlowState st, int64_t max_rt, Flo
                                         for (uint32_t b = 0; b < R.n_cbs; ++b)
                                             cb_on_complete(lcbs[b], t, qrt[k], (q.idx & F_ERROR) != 0);
                                 } else {  // DegradeSlot (a block's wait_ms: the breaker's index)
-                                    const int kb = degrade_block_index(lcbs, R.n_cbs, t);
+                                    const int kb = degrade_check(lcbs, R.n_cbs, t).kb;
                                     qd[k] = kb < 0 ? D_PASS : D_BLOCK_DEGRADE;
                                     qw[k] = kb < 0 ? 0 : kb;
                                 }
                             };
+                            // the same step with the breaker event log on (cbl: read once, outside the loops):
+                            // each breaker's state compared across its call, the entry's moves from degrade_check
+                            auto step_log = [&](uint32_t k) {
+                                const Payload q = qpay[k];
+                                const int64_t t = ts_base + (int64_t)q.ts_off;
+                                const uint64_t sq = cbl_seq + (q.idx & F_IDX);
+                                if (q.idx & F_EXIT) {
+                                    uint32_t sub = 0;
+                                    for (uint32_t b = 0; b < R.n_cbs; ++b) {
+                                        const int prev = lcbs[b].state;
+                                        if (R.n_cbs == 1) cb_on_complete_ws(lcbs[0], t, qrank_ws[k], qrt[k], (q.idx & F_ERROR) != 0);
+                                        else cb_on_complete(lcbs[b], t, qrt[k], (q.idx & F_ERROR) != 0);
+                                        if (lcbs[b].state != prev) cb_emit_complete(cbl, sq, lcbs[b], prev, t, res, b, sub++);
+                                    }
+                                } else {
+                                    const DegradeRes dr = degrade_check(lcbs, R.n_cbs, t);
+                                    if (dr.moved) cb_emit_entry(cbl, sq, dr.moved, dr.kb, t, res);
+                                    qd[k] = dr.kb < 0 ? D_PASS : D_BLOCK_DEGRADE;
+                                    qw[k] = dr.kb < 0 ? 0 : dr.kb;
+                                }
+                            };
                             uint32_t k = end;
                             if (seq_rest) {
-                                for (; k < cnt; ++k) step(k);
+                                if (cbl)
+                                    for (; k < cnt; ++k) step_log(k);
+                                else
+                                    for (; k < cnt; ++k) step(k);
                             } else if (k < cnt) {  // the event that ended the bulk part (a HALF_OPEN
                                                    // stretch after it is the next bulk part)
-                                step(k++);
+                                if (cbl) step_log(k++);
+                                else step(k++);
                             }
                             bulk_end = (int)k;
                         }
@@ -5365,6 +5473,7 @@ constexpr int kCbStage = 64 * kCbI + 64;
 template <int kW>
 struct CbLds {
     int64_t w[kW][5];  // per wave: total {ws, bad, tot}, first and last window
+    int64_t tc[2];     // the window's (bad, tot) at the round's first tripping exit
     uint32_t min, bad;
     uint32_t ts[kW][kCbStage], fx[kW][kCbStage];
     int64_t rt[kW][kCbStage];
@@ -5374,6 +5483,7 @@ struct CbRound {
     uint32_t trip;  // the first exit whose counts trip a CLOSED breaker (je: none, or !want_trip)
     bool bad;       // a window went back (inside the round or against the carry): the round is not taken
     int64_t first, last;  // the round's first and last windows (INT64_MAX / INT64_MIN: no exit)
+    int64_t tbad, ttot;   // trip < je: the window's counts at that exit (the breaker event's snapshot)
 };
 // One round of a flow's exits (kW waves x 64 lanes x kCbI consecutive exits from base, clipped at je) against
 // the carry: the stat window's counts as a segmented scan (segments = windows, non-decreasing) and, when
@@ -5477,7 +5587,7 @@ __device__ CbRound cb_round(CbLds<kW> &L, const CbDev &b, const CbAgg &carry, ui
     const int64_t lim = max(before, wlim);
     if (first != kCbNone && first < lim) mono = false;
     if (!mono) L.bad = 1;
-    CbRound out{carry, je, false, INT64_MAX, INT64_MIN};
+    CbRound out{carry, je, false, INT64_MAX, INT64_MIN, 0, 0};
     for (int w = 0; w < kW; ++w) {
         out.total = cb_combine(out.total, CbAgg{L.w[w][0], L.w[w][1], L.w[w][2]});
         out.first = min(out.first, L.w[w][3]);
@@ -5498,19 +5608,32 @@ __device__ CbRound cb_round(CbLds<kW> &L, const CbDev &b, const CbAgg &carry, ui
     CbAgg run{wave_shr1_i64(inc.ws, cwv.ws), wave_shr1_i64(inc.bad, cwv.bad), wave_shr1_i64(inc.tot, cwv.tot)};
     if (threadIdx.x == 0) L.min = je;
     __syncthreads();
+    uint32_t trip = je;
+    int64_t tb = 0, tt = 0;
     if (want_trip) {
-        uint32_t trip = je;
 #pragma unroll
         for (int i = 0; i < kCbI; ++i) {
             if (!((valm >> i) & 1u)) continue;
             run = cb_combine(run, CbAgg{wsv[i], (int64_t)((badm >> i) & 1u), 1});
-            if (trip == je && cb_trips(b, run.bad, run.tot)) trip = j0 + i;
+            if (trip == je && cb_trips(b, run.bad, run.tot)) {
+                trip = j0 + i;
+                tb = run.bad;
+                tt = run.tot;
+            }
         }
         if (trip < je) atomicMin(&L.min, trip);
     }
     __syncthreads();
     out.trip = L.min;
+    if (trip < je && trip == out.trip) {  // the one thread that holds the first tripping exit
+        L.tc[0] = tb;
+        L.tc[1] = tt;
+    }
     __syncthreads();
+    if (out.trip < je) {
+        out.tbad = L.tc[0];
+        out.ttot = L.tc[1];
+    }
     return out;
 }
 
@@ -5555,6 +5678,8 @@ __global__ __launch_bounds__(64 * kW) void k_cb_flows(FlowState st, FlowScratch 
                 if (probe < je) {  // fromOpenToHalfOpen: the probe passes
                     b.state = 2;
                     b.probe_t = ts_base + (int64_t)pay[probe].ts_off;
+                    if (st.cbl && threadIdx.x == 0)
+                        cb_emit(st.cbl, st.cbl_seq + (pay[probe].idx & F_IDX), b.probe_t, 0.0, res, 0, 0, 1u | 2u << 8);
                 }
             }
             for (uint32_t j = jb + threadIdx.x; j < je; j += 64 * kW) {
@@ -5575,6 +5700,7 @@ __global__ __launch_bounds__(64 * kW) void k_cb_flows(FlowState st, FlowScratch 
                     b.st_bad = carry.bad;
                     b.st_total = carry.tot;
                     cb_on_complete_ws(b, t, t - t % si, rt_in[q.idx & F_IDX], (q.idx & F_ERROR) != 0);
+                    if (st.cbl && threadIdx.x == 0) cb_emit_complete(st.cbl, st.cbl_seq + (q.idx & F_IDX), b, 2, t, res, 0, 0);
                     carry = CbAgg{b.st_start == kAbsent ? kCbNone : b.st_start, b.st_bad, b.st_total};
                     ++base;
                     continue;
@@ -5584,7 +5710,13 @@ __global__ __launch_bounds__(64 * kW) void k_cb_flows(FlowState st, FlowScratch 
                     seq = true;
                     break;
                 }
-                if (o.trip < je) cb_to_open(b, ts_base + (int64_t)pay[o.trip].ts_off);  // the first exit that trips it
+                if (o.trip < je) {  // the first exit that trips it
+                    const int64_t tt = ts_base + (int64_t)pay[o.trip].ts_off;
+                    cb_to_open(b, tt);
+                    if (st.cbl && threadIdx.x == 0)
+                        cb_emit(st.cbl, st.cbl_seq + (pay[o.trip].idx & F_IDX), tt, cb_snapshot(b, o.tbad, o.ttot), res, 0, 0,
+                                0u | 1u << 8);
+                }
                 carry = o.total;
                 base += kRound;
             }
@@ -5595,7 +5727,9 @@ __global__ __launch_bounds__(64 * kW) void k_cb_flows(FlowState st, FlowScratch 
                 for (uint32_t j = base; j < je; ++j) {
                     const Payload q = pay[j];
                     const int64_t t = ts_base + (int64_t)q.ts_off;
+                    const int prev = b.state;
                     cb_on_complete_ws(b, t, t - t % si, rt_in[q.idx & F_IDX], (q.idx & F_ERROR) != 0);
+                    if (st.cbl && threadIdx.x == 0) cb_emit_complete(st.cbl, st.cbl_seq + (q.idx & F_IDX), b, prev, t, res, 0, 0);
                 }
         }
         __syncthreads();
@@ -5643,7 +5777,7 @@ __global__ __launch_bounds__(kT) void k_cbt_plan(FlowState st, FlowScratch sc, c
 
 // a tiled flow's exit range [jb, je) and breaker
 __device__ __forceinline__ void cbt_flow(const FlowState &st, const FlowScratch &sc, uint32_t k, uint32_t &h,
-                                         uint32_t &jb, uint32_t &je, CbDev *&gb) {
+                                         uint32_t &jb, uint32_t &je, CbDev *&gb, uint32_t *res = nullptr) {
     const uint32_t nflows = sc.counters[2], nruns = sc.counters[1];
     h = sc.cbt_flow[k];
     const uint32_t fl = sc.cbf[h] & ~kCbTiled;
@@ -5652,6 +5786,7 @@ __device__ __forceinline__ void cbt_flow(const FlowState &st, const FlowScratch 
     jb = sc.run_start[r0];
     je = sc.run_end[r1 - 1];
     gb = st.cbs + st.res[sc.run_slot[r0]].cb_off;
+    if (res) *res = sc.run_slot[r0];
 }
 
 template <bool kTrip>
@@ -5700,7 +5835,11 @@ __global__ __launch_bounds__(64 * kCbW) void k_cbt_tiles(FlowState st, FlowScrat
         } else {
             if (sc.cbt_state[k] != 1 || b.state != 0) continue;  // taken, CLOSED
             const CbRound o = cb_round(L, b, sc.cbt[t].carry, base, je, true, pay, sc.rt_sorted, ts_base);
-            if (threadIdx.x == 0 && o.trip < je) atomicMin(&sc.cbt_trip[k], o.trip);
+            if (threadIdx.x == 0 && o.trip < je) {
+                atomicMin(&sc.cbt_trip[k], o.trip);
+                sc.cbt[t].tbad = o.tbad;  // k_cbt_fin reads the first tripping tile's
+                sc.cbt[t].ttot = o.ttot;
+            }
         }
     }
 }
@@ -5745,9 +5884,9 @@ __global__ __launch_bounds__(kT) void k_cbt_fin(FlowState st, FlowScratch sc, co
     const uint32_t nf = sc.cbt_ctl[0];
     for (uint32_t k = blockIdx.x * kT + threadIdx.x; k < nf; k += gridDim.x * kT) {
         if (sc.cbt_state[k] != 1) continue;
-        uint32_t h, jb, je;
+        uint32_t h, jb, je, res;
         CbDev *gb;
-        cbt_flow(st, sc, k, h, jb, je, gb);
+        cbt_flow(st, sc, k, h, jb, je, gb, &res);
         CbDev b = *gb;
         const uint32_t trip = sc.cbt_trip[k];
         if (!(pay[jb].idx & F_EXIT)) {  // entries: an OPEN breaker's probe passes (fromOpenToHalfOpen)
@@ -5755,10 +5894,20 @@ __global__ __launch_bounds__(kT) void k_cbt_fin(FlowState st, FlowScratch sc, co
                 b.state = 2;
                 b.probe_t = ts_base + (int64_t)pay[trip].ts_off;
                 *gb = b;
+                if (st.cbl)
+                    cb_emit(st.cbl, st.cbl_seq + (pay[trip].idx & F_IDX), b.probe_t, 0.0, res, 0, 0, 1u | 2u << 8);
             }
             continue;
         }
-        if (b.state == 0 && trip < je) cb_to_open(b, ts_base + (int64_t)pay[trip].ts_off);
+        if (b.state == 0 && trip < je) {
+            const int64_t tt = ts_base + (int64_t)pay[trip].ts_off;
+            cb_to_open(b, tt);
+            if (st.cbl) {
+                const CbTile &T = sc.cbt[sc.cbt_off[k] + (trip - jb) / kCbRound];  // the tile that found it
+                cb_emit(st.cbl, st.cbl_seq + (pay[trip].idx & F_IDX), tt, cb_snapshot(b, T.tbad, T.ttot), res, 0, 0,
+                        0u | 1u << 8);
+            }
+        }
         const CbAgg c = sc.cbt_total[k];
         b.st_start = c.ws == kCbNone ? kAbsent : c.ws;
         b.st_bad = c.bad;
@@ -6774,6 +6923,8 @@ FlowState FlowEngine::state() const {
     s.ntslot = lru ? ntbase * (uint32_t)kMaxParamIdx : 0;
     s.seq_base = seq;
     s.octx = has_pair_rules ? d_octx.p : nullptr;
+    s.cbl = cbev.on ? cbev.dev.p : nullptr;
+    s.cbl_seq = cbev.seq;
     return s;
 }
 
@@ -7443,6 +7594,8 @@ int FlowEngine::load_degrade_rules(const sga_degrade_rule *rules, size_t n) {
     h_cbs = nc;
     h_cb_src = nsrc;
     h_cb_idx = nidx;
+    ++cbev.epoch;  // pending breaker events keep the epoch of the list their k indexes
+    if (cbev.on) cb_events_sync();
     d_cbs.alloc(std::max<size_t>(nc.size(), 1));
     if (!nc.empty())
         SGA_HIP_CHECK(hipMemcpyAsync(d_cbs.p, nc.data(), nc.size() * sizeof(CbDev), hipMemcpyHostToDevice, stream));
@@ -8103,6 +8256,7 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
             }
         }
         seq += m;  // a chunk that reached its prologue keeps its sequence numbers (stamps, pair births), failed or not
+        if (cbev.on) cbev.seq += m;
         if (rc) return rc;
         b += m;
     }
@@ -8198,6 +8352,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
     SGA_HIP_CHECK(hipGetLastError());
     block_log_pass(c);  // after k_lfail: a refused chunk answers -1 and logs nothing
     seq += n;
+    if (cbev.on) cbev.seq += n;
     return 0;
 }
 
@@ -8787,6 +8942,60 @@ int FlowEngine::block_log_drain(int64_t before_ms, sga_block_row *rows, size_t c
         if (x.origin != y.origin) return x.origin < y.origin;
         if (x.tag_kind != y.tag_kind) return x.tag_kind < y.tag_kind;
         return x.tag < y.tag;
+    });
+    return 0;
+}
+
+// ---- breaker events
+int FlowEngine::cb_events_enable(uint32_t max_events) {
+    if (!nres) return SGA_EINVAL;
+    if (max_events == 0) max_events = 1u << 16;  // the default: a choice, not a measurement
+    if (max_events > (1u << 26)) return SGA_EINVAL;
+    uint32_t cap = 64;
+    while (cap < max_events) cap <<= 1;
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (cbev.on) {  // an empty log may be resized
+        unsigned long long used = 0;
+        SGA_HIP_CHECK(hipMemcpy(&used, cbev.ctl.p, 8, hipMemcpyDeviceToHost));
+        if (used) return SGA_EINVAL;
+        if (cap == cbev.cap) return 0;
+    } else {
+        cbev.ctl.alloc(2);
+        cbev.dev.alloc(1);
+        cbev.seq = 0;
+    }
+    cbev.rec.alloc(cap);
+    SGA_HIP_CHECK(hipMemsetAsync(cbev.ctl.p, 0, 16, stream));
+    cbev.cap = cap;
+    cbev.on = true;
+    cb_events_sync();
+    return 0;
+}
+
+// the device's copy of the log's header, after anything in it changed (no chunk is in flight: the callers waited)
+void FlowEngine::cb_events_sync() {
+    const CbLog h{cbev.rec.p, cbev.ctl.p, cbev.cap, cbev.epoch};
+    SGA_HIP_CHECK(hipMemcpyAsync(cbev.dev.p, &h, sizeof(h), hipMemcpyHostToDevice, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// Copy out, then sort on the host: records are appended in the order the kernels reach them, which is the
+// reference's order only inside one flow; (seq, sub) restores it over the whole log, and transitions are few.
+int FlowEngine::cb_events_drain(sga_cb_event *ev, size_t cap, size_t *n, uint64_t *lost) {
+    if (!cbev.on || !n || (cap && !ev)) return SGA_EINVAL;
+    *n = 0;
+    unsigned long long ctl[2] = {0, 0};
+    SGA_HIP_CHECK(hipMemcpyAsync(ctl, cbev.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    const size_t cnt = (size_t)std::min<unsigned long long>(ctl[0], cbev.cap);
+    *n = cnt;
+    if (cnt > cap) return SGA_ERANGE;  // nothing removed, the lost counter kept
+    if (cnt) SGA_HIP_CHECK(hipMemcpyAsync(ev, cbev.rec.p, cnt * sizeof(sga_cb_event), hipMemcpyDeviceToHost, stream));
+    if (ctl[0] || ctl[1]) SGA_HIP_CHECK(hipMemsetAsync(cbev.ctl.p, 0, 16, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (lost) *lost = ctl[1];
+    std::sort(ev, ev + cnt, [](const sga_cb_event &x, const sga_cb_event &y) {
+        return x.seq != y.seq ? x.seq < y.seq : x.sub < y.sub;
     });
     return 0;
 }

@@ -211,6 +211,16 @@ struct BlogTab {
 constexpr uint32_t kBlogProbe = 128;  // linear probes before a tuple counts as lost
 constexpr uint8_t kBlogScalar = 0, kBlogList = 1;  // sga_block_row::tag_kind
 
+// Breaker events (sga_cb_events_enable): an append buffer of sga_cb_event in HBM behind one atomic counter.  The
+// kernels that write a breaker's state append one record per transition (flow.hip cb_emit); a record that finds
+// the buffer full only counts in ctl[1].  The header lives in device memory (rewritten when the log is enabled or
+// resized and when the degrade rules are loaded); FlowState carries one pointer to it, null while the log is off.
+struct CbLog {
+    sga_cb_event *rec;
+    unsigned long long *ctl;  // [0] records claimed (may pass cap) [1] lost
+    uint32_t cap, epoch;      // epoch: sga_load_degrade_rules calls so far
+};
+
 struct FlowState {
     int64_t *node;
     FlowRuleDev *rules;
@@ -258,6 +268,8 @@ struct FlowState {
     uint32_t nprid, ntslot;      // parameter-rule ids, thread-map owner slots
     uint64_t seq_base;           // event sequence of the batch's first event
     const PairCtx *octx;         // null unless the loaded FlowRules hold one limited to an origin or "other", or a CHAIN one
+    const CbLog *cbl;            // breaker events (null: off)
+    uint64_t cbl_seq;            // the chunk's first event: events submitted since the log was enabled
 };
 constexpr uint32_t kLruThread = 1u << 31;
 
@@ -278,6 +290,7 @@ struct CbAgg {
 struct CbTile {  // one tile of a long exit-only breaker flow (k_cbt_*)
     CbAgg agg, carry;
     int64_t first, last;  // windows
+    int64_t tbad, ttot;   // k_cbt_tiles<1>: the window's counts at the tile's first tripping exit (breaker events)
     uint32_t bad;         // a window went back inside the tile
 };
 
@@ -572,6 +585,19 @@ struct FlowEngine {
     void block_log_pass(const Chunk &c);
     int block_log_drain(int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n, uint64_t *lost_events,
                         int64_t *lost_count);
+    // Breaker events (CbLog): off until cb_events_enable -- no chunk launches or allocates anything for it.  The
+    // deciding kernels append; the drain copies out and sorts by (seq, sub) on the host.
+    struct CbEvents {
+        bool on = false;
+        uint32_t cap = 0, epoch = 0;
+        uint64_t seq = 0;  // events submitted since the log was enabled (every entry point)
+        DevBuf<sga_cb_event> rec;
+        DevBuf<unsigned long long> ctl;
+        DevBuf<CbLog> dev;  // FlowState::cbl
+    } cbev;
+    void cb_events_sync();
+    int cb_events_enable(uint32_t max_events);
+    int cb_events_drain(sga_cb_event *ev, size_t cap, size_t *n, uint64_t *lost);
     // per rule in device order (FlowState::rules / prules / cbs): its index in the array the loader was given
     std::vector<uint32_t> h_flow_idx, h_prule_idx, h_cb_idx;
     int block_rule_index(int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index) const;

@@ -24,6 +24,8 @@ Same names and argument meaning as the Java API the engine replaces:
                                   command center's tree / jsonTree walk them -> the `parent` of entry / submit on a
                                   LocalSentinel(tree=True), LocalSentinel.tree_rows / invocation_tree
   FlowRuleManager.getRules and its siblings -> the managers' get_rules
+  EventObserverRegistry.addStateChangeObserver  CORE/slots/block/degrade/circuitbreaker/EventObserverRegistry.java
+                                  -> LocalSentinel.observers (fed by the engine's breaker event log, sga_cb_events_*)
 BlockException subclasses as in CORE/slots/block/BlockException.java and its subclasses.
 
 Every decision is computed by the HIP engine (libsentinel_amd.so).  The mocked
@@ -33,6 +35,7 @@ Resources are registered up front (dense ids), like CtSph's chain map keys.
 import ctypes as C
 import struct
 from dataclasses import dataclass
+from enum import IntEnum
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -266,6 +269,73 @@ class Entry:
                            context=[self._owner.context_id(self.context)] if self.context else None)
 
 
+class CircuitBreakerState(IntEnum):
+    """CircuitBreaker.State, numbered as sga_circuit_breaker_state and sga_cb_event do."""
+    CLOSED = 0
+    OPEN = 1
+    HALF_OPEN = 2
+
+
+@dataclass
+class BreakerEvent:
+    """One sga_cb_event with its rule resolved: the DegradeRule object the manager loaded (None while nothing was
+    loaded through this sentinel).  snapshot_value is None exactly when the reference passes null (new_state is
+    not OPEN)."""
+    seq: int
+    sub: int
+    ts: int
+    resource: int
+    breaker: int
+    epoch: int
+    prev_state: CircuitBreakerState
+    new_state: CircuitBreakerState
+    rule: object
+    snapshot_value: Optional[float]
+
+
+BREAKER_EVENT_DTYPE = np.dtype([("ts", "<i8"), ("value", "<f8"), ("seq", "<u8"), ("resource", "<u4"),
+                                ("breaker", "<u4"), ("epoch", "<u4"), ("sub", "<u2"), ("prev", "u1"), ("next", "u1")])
+
+
+class EventObserverRegistry:
+    """EventObserverRegistry's state-change observers of one LocalSentinel (sentinel.observers).  The first observer
+    turns the engine's breaker event log on; from then on every host call of the sentinel that can move a breaker
+    drains the log and calls fn(prev_state, new_state, rule, snapshot_value) per transition, in the reference's
+    order, every observer in registration order."""
+
+    def __init__(self, sentinel: "LocalSentinel"):
+        self._s = sentinel
+        self._observers: Dict[str, object] = {}
+
+    def add_state_change_observer(self, name: str, fn) -> None:
+        if name is None or fn is None:
+            raise ValueError("name and observer cannot be null")
+        self._s.enable_breaker_events()
+        self._observers[name] = fn
+
+    def remove_state_change_observer(self, name: str) -> bool:
+        return self._observers.pop(name, None) is not None
+
+    def get_state_change_observers(self) -> list:
+        return list(self._observers.values())
+
+    def dispatch(self, events) -> None:
+        """Every event to every observer.  An observer that raises ends the delivery of its event; the events after
+        it are not lost: they stay with the sentinel and go out with the next delivery, ahead of newer ones.  The
+        exception surfaces from the call that delivered (entry, exit, submit, load_rules, ...), as the reference's
+        observers throw into the thread that moved the breaker."""
+        events = list(events)
+        for i, ev in enumerate(events):
+            try:
+                for fn in list(self._observers.values()):
+                    fn(ev.prev_state, ev.new_state, ev.rule, ev.snapshot_value)
+            except BaseException:
+                held = getattr(self._s, "_held_events", None)
+                if held is not None:
+                    held[:0] = events[i + 1:]
+                raise
+
+
 class LocalSentinel:
     """The local slot chain (StatisticSlot, ParamFlowSlot, FlowSlot, DegradeSlot) on one engine."""
 
@@ -323,6 +393,10 @@ class LocalSentinel:
         self._loaded: Dict[int, object] = {}
         # String.valueOf(args[paramIdx]) of the parameter blocks entry() raised, by (tag, tag_kind): bounded
         self.param_texts: Dict[tuple, str] = {}
+        self.observers = EventObserverRegistry(self)
+        self.breaker_event_cap = 0  # 0: the breaker event log is off
+        self.breaker_events_lost = 0  # transitions that found the log full, over all drains
+        self._held_events: List[BreakerEvent] = []  # drained ahead of a rule reload, not yet handed out
         self.block_log_rows = 0
         if block_log:
             rows = 0 if block_log is True else int(block_log)
@@ -340,9 +414,64 @@ class LocalSentinel:
     def resource_id(self, name: str) -> int:
         return self.ids[name]
 
+    # ---- breaker events (EventObserverRegistry)
+    def enable_breaker_events(self, max_events: int = 0) -> None:
+        """sga_cb_events_enable: turns the engine's breaker event log on (0: its default of 65,536 records), or
+        resizes it while it is empty."""
+        if self.breaker_event_cap and not max_events:
+            return
+        check(_lib.load().sga_cb_events_enable(self.engine.handle, int(max_events)), self.engine.handle,
+              "cbEventsEnable")
+        self.breaker_event_cap = max(64, 1 << (int(max_events) - 1).bit_length()) if max_events else 1 << 16
+
+    def breaker_event_records(self):
+        """sga_cb_events_drain: (records, lost) -- a BREAKER_EVENT_DTYPE array sorted by (seq, sub), and the
+        transitions that found the log full since the last drain."""
+        n, lost = C.c_size_t(), C.c_uint64()
+        cap = self.breaker_event_cap
+        while True:
+            out = np.zeros(max(1, cap), dtype=BREAKER_EVENT_DTYPE)
+            rc = _lib.load().sga_cb_events_drain(self.engine.handle, out.ctypes.data, cap, C.byref(n), C.byref(lost))
+            if rc != _lib.SGA_ERANGE:
+                break
+            cap = int(n.value)  # the log was resized behind this sentinel's back: take what it needs
+        check(rc, self.engine.handle, "cbEventsDrain")
+        return out[:n.value].copy(), int(lost.value)
+
+    def breaker_events(self) -> List[BreakerEvent]:
+        """Drains the log: the pending transitions in the reference's notification order, each with the
+        DegradeRule its (resource, breaker) named in the list loaded when it happened."""
+        out, self._held_events = self._held_events + self._drain_breaker_events(), []
+        return out
+
+    def _drain_breaker_events(self) -> List[BreakerEvent]:
+        recs, lost = self.breaker_event_records()
+        self.breaker_events_lost += lost
+        out = []
+        for r in recs:
+            nxt = CircuitBreakerState(int(r["next"]))
+            out.append(BreakerEvent(int(r["seq"]), int(r["sub"]), int(r["ts"]), int(r["resource"]), int(r["breaker"]),
+                                    int(r["epoch"]), CircuitBreakerState(int(r["prev"])), nxt,
+                                    self.block_rule(Decision.BLOCK_DEGRADE, int(r["resource"]), int(r["breaker"])),
+                                    float(r["value"]) if nxt == CircuitBreakerState.OPEN else None))
+        return out
+
+    def _notify(self) -> None:
+        """After a host call that waited for its decisions: deliver what the log holds to the observers."""
+        if self.breaker_event_cap and self.observers._observers:
+            self.observers.dispatch(self.breaker_events())
+
     # ---- batched form: the engine's native interface
     def submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None,
                context=None, parent=None):
+        """Events in arrival order (see _submit); with state-change observers registered, the breaker transitions
+        of the call are delivered before it returns."""
+        out = self._submit(kind, resource, ts, acquire, flags, rt, param, param_values, origin, context, parent)
+        self._notify()
+        return out
+
+    def _submit(self, kind, resource, ts, acquire, flags=None, rt=None, param=None, param_values=None, origin=None,
+                context=None, parent=None):
         """Events in arrival order.  param_values: the values of Collection / array arguments
         (events flagged SGA_EV_PARAM_LIST = 16 carry param = offset << 32 | count into it).
         origin: each event's origin id (origin_id; 0 = none), on a sentinel with registered origins.
@@ -424,6 +553,7 @@ class LocalSentinel:
                                           int(flags), int(rt), int(param), pv.ctypes.data if pv is not None else None,
                                           0 if pv is None else len(pv), C.byref(t))
         check(rc, self.engine.handle, "eventSubmit")
+        self._notify()
         return int(t.value)
 
     def event_poll(self, ticket):
@@ -433,6 +563,7 @@ class LocalSentinel:
         if rc == -11:  # SGA_EAGAIN
             return None
         check(rc, self.engine.handle, "eventPoll")
+        self._notify()
         return int(d.value), int(w.value)
 
     def event_post(self, kind, resource, ts, acquire, flags=0, rt=0, param=0, param_values=None) -> int:
@@ -444,6 +575,7 @@ class LocalSentinel:
                                         int(rt), int(param), pv.ctypes.data if pv is not None else None,
                                         0 if pv is None else len(pv), C.byref(t))
         check(rc, self.engine.handle, "eventPost")
+        self._notify()
         return int(t.value)
 
     def event_one(self, kind, resource, ts, acquire, flags=0, rt=0, param=0, param_values=None):
@@ -454,6 +586,7 @@ class LocalSentinel:
                                        int(rt), int(param), pv.ctypes.data if pv is not None else None,
                                        0 if pv is None else len(pv), C.byref(d), C.byref(w))
         check(rc, self.engine.handle, "eventOne")
+        self._notify()
         return int(d.value), int(w.value)
 
     def submit_device(self, kind, resource, ts_base, ts_off, acquire, flags=None, rt=None, param=None,
@@ -963,6 +1096,10 @@ class DegradeRuleManager:
         return list(getattr(self, "_rules", []))
 
     def load_rules(self, rules: List[DegradeRule]) -> int:
+        # pending breaker events name breakers of the list still loaded: deliver (or hold) them against it first
+        if getattr(self.s, "breaker_event_cap", 0):
+            self.s._held_events += self.s._drain_breaker_events()
+            self.s._notify()
         self._rules = list(rules)
         rules = [r for r in rules if r.resource in self.s.ids]
         arr = (SgaDegradeRule * max(1, len(rules)))()
