@@ -946,6 +946,71 @@ int sga_cluster_metric_nodes(sga_engine *e, int64_t now, sga_cluster_metric_node
 int sga_cluster_metric_nodes_device(sga_engine *e, int64_t now, sga_cluster_metric_node *d_out, size_t cap,
                                     uint32_t *d_n, void *hip_stream);
 
+/* ---- gateway flow rules: request fields -> argument vectors (no struct changes: new entry points only) ----
+ * GatewayParamParser.parseParameterFor (GW = sentinel-adapter/sentinel-api-gateway-adapter-common/src/main/java/
+ * com/alibaba/csp/sentinel/adapter/gateway/common; GW/param/GatewayParamParser.java:51-174) for a whole batch:
+ * per event and rule of its resource, pick a request field, match it against the rule's pattern, and hash the
+ * resulting string into the 64-bit key the parameter maps use.  The converted ParamFlowRules
+ * (GW/rule/GatewayRuleConverter.java:49-86) are loaded through sga_load_param_rules like any other; this table
+ * only says how each resource's argument vector is made.
+ *
+ * One item per valid GatewayFlowRule.  index: the rule's paramItem index as GatewayRuleManager assigned it
+ * (GW/rule/GatewayRuleManager.java:179-237), -1 for a rule without a paramItem.  field: a column of the request
+ * field table.  Items of one resource that share an index: the last in array order wins the slot.  A resource's
+ * argument count is (its items with index >= 0) + (1 if it has an item of index -1): at most 64. */
+typedef struct sga_gateway_item {
+    uint32_t resource;
+    int32_t index;
+    uint32_t field;
+    int32_t match_strategy; /* 0 EXACT, 2 REGEX, 3 CONTAINS; 1 (PREFIX) and everything else keep the value */
+    uint32_t pattern_off;   /* the pattern's UTF-8 bytes in patterns_blob */
+    uint32_t pattern_len;
+    int32_t resource_mode;  /* 0 route id, 1 custom API name */
+    uint8_t has_pattern;    /* 0: pattern null or empty -- no matching */
+    uint8_t reserved[3];
+} sga_gateway_item;
+#define SGA_GW_EXACT 0
+#define SGA_GW_REGEX 2
+#define SGA_GW_CONTAINS 3
+#define SGA_GW_NULL 0xFFFFFFFFu /* a field length: the request has no such field (0 is the empty string) */
+#define SGA_GW_SEED 0x5E47ull   /* a string's key: XXH64 of its UTF-8 bytes with this seed */
+
+/* Replaces the table (n_items = 0 clears it: sga_gateway_parse* then launch nothing).  After
+ * sga_flow_set_resources.  SGA_EINVAL: a resource or field out of range, an index outside [-1, 64), a pattern
+ * outside the blob; SGA_ERANGE: a resource with more than 64 arguments. */
+int sga_gateway_load(sga_engine *e, const sga_gateway_item *items, size_t n_items, const uint8_t *patterns_blob,
+                     size_t blob_len, uint32_t n_fields);
+/* The largest argument count of a loaded resource (0: no table).  sga_gateway_parse* write each event's vector
+ * at value_base + i * 2 * max_args: the value buffer holds value_base + 2 * max_args * n words. */
+int sga_gateway_max_args(sga_engine *e, uint32_t *out);
+/* XXH64(bytes, SGA_GW_SEED): the key sga_gateway_parse* give a string ("$NM" and "$D" included). */
+uint64_t sga_gateway_string_key(const uint8_t *bytes, size_t len);
+/* Over DEVICE buffers, asynchronous on `hip_stream` with the ordering of sga_submit_events_device; n <= max_batch.
+ * d_mode[i]: the request's resource mode.  The values are read as aligned 4-byte words: d_bytes must be readable from
+ * the 4-byte boundary at or below it to the one at or above d_bytes + n_bytes (any hipMalloc'd buffer is).
+ *  Field k of event i is d_bytes[d_field_off[i * n_fields + k] ..
+ * + d_field_len[i * n_fields + k]) (any offset, any length; SGA_GW_NULL: null).  d_regex_bits (may be NULL: every
+ * REGEX item matches): bit `index` of word i = the REGEX item at that index matches event i's value.
+ * For every event whose resource has items: the SGA_EV_ARGS words of parseParameterFor's array go to
+ * d_param_values[value_base + i * 2 * max_args ..), d_param[i] = offset << 32 | nargs, d_flags[i] |= SGA_EV_ARGS
+ * (nargs 0 when a rule's resource mode differs from d_mode[i]).  Null fields and unwritten slots are
+ * SGA_ARG_NULL; strings are SGA_ARG_SCALAR with sga_gateway_string_key.  Every other event is left as given.
+ * An event whose field slice leaves the blob or whose vector leaves the value buffer (n_values words, fewer than
+ * 2^32 - 1) gets d_param[i] = 0xFFFFFFFF << 32 with SGA_EV_ARGS -- an empty vector past the buffer, which every
+ * submit entry refuses with its chunk -- and sga_events_device_status reports SGA_EINVAL. */
+int sga_gateway_parse_device(sga_engine *e, const uint32_t *d_resource, const uint8_t *d_mode,
+                             const uint32_t *d_field_off, const uint32_t *d_field_len, const uint8_t *d_bytes,
+                             size_t n_bytes, const uint64_t *d_regex_bits, size_t n, uint8_t *d_flags,
+                             uint64_t *d_param, uint64_t *d_param_values, size_t n_values, size_t value_base,
+                             void *hip_stream);
+/* The same over HOST buffers, synchronous, any n (chunks of max_batch inside); like the device form it leaves the
+ * words of param_values it does not write as they were.  SGA_EINVAL for what the device
+ * form reports through the status call (the outputs then hold the poisoned events). */
+int sga_gateway_parse(sga_engine *e, const uint32_t *resource, const uint8_t *mode, const uint32_t *field_off,
+                      const uint32_t *field_len, const uint8_t *bytes, size_t n_bytes, const uint64_t *regex_bits,
+                      size_t n, uint8_t *flags, uint64_t *param, uint64_t *param_values, size_t n_values,
+                      size_t value_base);
+
 /* Optional helper for tools: HIP stream of the engine (hipStream_t as void*). */
 void *sga_engine_stream(sga_engine *e);
 

@@ -5,5 +5,6 @@ libsentinel_amd.so (C-ABI: include/sentinel_amd.h).  This package is the
 host-side mirror of the reference's Java interface for that path.
 """
 from ._lib import EngineError, LIB_PATH  # noqa: F401
+from .gateway import GatewayFlowRule, GatewayParamFlowItem, GatewayRuleManager  # noqa: F401
 
-__all__ = ["EngineError", "LIB_PATH"]
+__all__ = ["EngineError", "LIB_PATH", "GatewayFlowRule", "GatewayParamFlowItem", "GatewayRuleManager"]

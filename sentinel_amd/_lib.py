@@ -126,6 +126,12 @@ class SgaCbEvent(C.Structure):  # sga_cb_event: one circuit breaker transition
                 ("next", C.c_uint8)]
 
 
+class SgaGatewayItem(C.Structure):  # sga_gateway_item: one valid GatewayFlowRule of the parser's table
+    _fields_ = [("resource", C.c_uint32), ("index", C.c_int32), ("field", C.c_uint32), ("match_strategy", C.c_int32),
+                ("pattern_off", C.c_uint32), ("pattern_len", C.c_uint32), ("resource_mode", C.c_int32),
+                ("has_pattern", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 SGA_TAG_SCALAR, SGA_TAG_LIST = 0, 1  # sga_block_row.tag_kind
 
 SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
@@ -265,6 +271,16 @@ SIGNATURES = {
     "sga_cb_events_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_cb_events_drain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_uint64)]),
+    "sga_gateway_load": (C.c_int, [C.c_void_p, C.POINTER(SgaGatewayItem), C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.c_uint32]),
+    "sga_gateway_max_args": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "sga_gateway_string_key": (C.c_uint64, [C.c_void_p, C.c_size_t]),
+    "sga_gateway_parse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_size_t, C.c_void_p]),
+    "sga_gateway_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_size_t]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_wire_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(SgaWireBatch)]),

@@ -24,6 +24,7 @@ import uuid
 from typing import Callable, Dict, List, Optional, Tuple
 from urllib.parse import unquote_plus
 
+from .gateway import GatewayFlowRule, GatewayParamFlowItem
 from .javautil import double_to_string, is_blank
 from .local import ENTRY_NODE, MetricNode, NodeView, SystemRule
 from .rules import (AuthorityRule, ClusterFlowConfig, DegradeRule, FlowRule, ParamFlowClusterConfig, ParamFlowItem,
@@ -222,7 +223,8 @@ def _camel(name: str) -> str:
 
 
 _NESTED = {(FlowRule, "cluster_config"): ClusterFlowConfig, (ParamFlowRule, "cluster_config"): ParamFlowClusterConfig,
-           (ParamFlowRule, "param_flow_item_list"): ParamFlowItem}
+           (ParamFlowRule, "param_flow_item_list"): ParamFlowItem,
+           (GatewayFlowRule, "param_item"): GatewayParamFlowItem}
 
 
 def rule_to_bean(rule) -> dict:
@@ -413,6 +415,9 @@ class CommandCenter:
         if getattr(sentinel, "tree", False):  # the sentinel records the invocation tree's edges
             self.register("tree", "get metrics in tree mode, use id to specify detailed tree root", self._tree)
             self.register("jsonTree", "get tree node VO start from root node", self._json_tree)
+        if "gateway" in self.managers:  # a gateway.GatewayRuleManager: the api-gateway adapter's two handlers
+            self.register("gateway/getRules", "Fetch all gateway rules", self._gateway_get_rules)
+            self.register("gateway/updateRules", "Update gateway rules", self._gateway_update_rules)
         self.new_id: Callable[[], object] = uuid.uuid4  # NodeVo's UUID.randomUUID()
 
     def register(self, name: str, desc: str, fn: Callable[[Dict[str, str]], str]) -> None:
@@ -480,6 +485,27 @@ class CommandCenter:
         if data:
             data = unquote_plus(data, encoding="utf-8")
         return self._load("param", ParamFlowRule, data)
+
+    def _gateway_get_rules(self, p):
+        """GetGatewayRuleCommandHandler: JSON.toJSONString(GatewayRuleManager.getRules())."""
+        return self._rules_json("gateway")
+
+    def _gateway_update_rules(self, p):
+        """UpdateGatewayRuleCommandHandler: a blank data is "Bad data"; data that does not decode or parse answers
+        "decode gateway rule data error" (the reference lets fastjson's exception reach the server, which answers
+        a failure too); otherwise the rules are loaded and the answer is "success"."""
+        data = p.get("data")
+        if data is None or not data.strip():
+            raise ValueError("Bad data")
+        try:
+            arr = json.loads(unquote_plus(data, encoding="utf-8", errors="strict"))
+            rules = [rule_from_bean(GatewayFlowRule, o) for o in (arr or [])]
+        except (ValueError, TypeError):
+            raise ValueError("decode gateway rule data error")
+        if any(isinstance(o, dict) and o.get("clusterMode") for o in (arr or [])):
+            raise ValueError("cluster-mode gateway rules do not exist in the reference: refused")
+        self.managers["gateway"].load_rules(rules)
+        return "success"
 
     def _cluster_node(self, p):
         now = self.clock()

@@ -5,6 +5,7 @@
 #include "cluster_exact.hpp"  // the window record layout (rec_units)
 #include "concurrent.hpp"
 #include "flow.hpp"
+#include "gateway.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -587,6 +588,7 @@ struct Engine {
 
     // ---- local flow engine
     FlowEngine flow;
+    sga::GatewayEngine gateway;  // sga_gateway_*: request fields -> argument vectors, ahead of any submit entry
 
     int32_t uni_S = 0, uni_W = 0, uni_iv = 0;  // ClusterState::uni_S (sync_device)
     // pset 1: the second pipelined scratch set's dense table
@@ -2545,6 +2547,67 @@ int sga_submit_events_tree_device(sga_engine *e, const uint8_t *d_kind, const ui
                                             d_context, d_parent);
         g.leave_stream(s);
         return rc;
+    });
+}
+
+int sga_gateway_load(sga_engine *e, const sga_gateway_item *items, size_t n_items, const uint8_t *patterns_blob,
+                     size_t blob_len, uint32_t n_fields) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.gateway.load(items, n_items, patterns_blob, blob_len, n_fields, g.flow.nres, g.stream, &g.err);
+    });
+}
+
+int sga_gateway_max_args(sga_engine *e, uint32_t *out) {
+    if (!out) return SGA_EINVAL;
+    return guarded(e, [&](Engine &g) {
+        *out = g.gateway.max_args;
+        return SGA_OK;
+    });
+}
+
+uint64_t sga_gateway_string_key(const uint8_t *bytes, size_t len) {
+    return (len && !bytes) || len > 0xFFFFFFFFu ? 0 : sga::gateway_string_key(bytes, len);
+}
+
+int sga_gateway_parse_device(sga_engine *e, const uint32_t *d_resource, const uint8_t *d_mode,
+                             const uint32_t *d_field_off, const uint32_t *d_field_len, const uint8_t *d_bytes,
+                             size_t n_bytes, const uint64_t *d_regex_bits, size_t n, uint8_t *d_flags,
+                             uint64_t *d_param, uint64_t *d_param_values, size_t n_values, size_t value_base,
+                             void *hip_stream) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway.loaded() || n == 0) return SGA_OK;  // no table: nothing is launched
+        if (n > g.cfg.max_batch) return SGA_ERANGE;
+        if (!d_resource || !d_mode || !d_flags || !d_param || !d_param_values) return SGA_EINVAL;
+        if (n_values >= 0xFFFFFFFFull) return SGA_EINVAL;  // offsets are 32 bits; the refused events' word is past it
+        if (g.gateway.n_fields && (!d_field_off || !d_field_len)) return SGA_EINVAL;
+        if (n_bytes && !d_bytes) return SGA_EINVAL;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        if (!g.flow.d_gate.p) {  // the device entry's status words (FlowEngine::device_status)
+            g.flow.d_gate.alloc(2);
+            SGA_HIP_CHECK(hipMemsetAsync(g.flow.d_gate.p, 0, 8, g.stream));
+        }
+        hipStream_t s = g.enter_stream(hip_stream);
+        g.gateway.launch(d_resource, d_mode, d_field_off, d_field_len, d_bytes, n_bytes, d_regex_bits, (uint32_t)n,
+                         d_flags, d_param, d_param_values, n_values, value_base, 0, g.flow.d_gate.p + 1, s);
+        g.leave_stream(s);
+        return SGA_OK;
+    });
+}
+
+int sga_gateway_parse(sga_engine *e, const uint32_t *resource, const uint8_t *mode, const uint32_t *field_off,
+                      const uint32_t *field_len, const uint8_t *bytes, size_t n_bytes, const uint64_t *regex_bits,
+                      size_t n, uint8_t *flags, uint64_t *param, uint64_t *param_values, size_t n_values,
+                      size_t value_base) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway.loaded() || n == 0) return SGA_OK;
+        if (!resource || !mode || !flags || !param || !param_values) return SGA_EINVAL;
+        if (n_values >= 0xFFFFFFFFull) return SGA_EINVAL;
+        if (g.gateway.n_fields && (!field_off || !field_len)) return SGA_EINVAL;
+        if (n_bytes && !bytes) return SGA_EINVAL;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.gateway.parse_host(resource, mode, field_off, field_len, bytes, n_bytes, regex_bits, n, flags, param,
+                                    param_values, n_values, value_base, g.cfg.max_batch, g.stream);
     });
 }
 

@@ -683,6 +683,17 @@ class LocalSentinel:
             not isinstance(args[0], (list, tuple)) else None
         return Entry(self, rid, now, batch_count, param, int(wait[0]), inbound, args, origin, context, parent)
 
+    def gateway_entry(self, resource: str, mode: int, request, now: int, **kw) -> Entry:
+        """A gateway filter's entry of one route or API group (a sentinel with a gateway.GatewayRuleManager):
+        GatewayParamParser.parseParameterFor(resource, request, rule -> rule.resourceMode == mode) on the host, then
+        entry(resource, now, args=...).  request: {("header", "X-Flag"): "v", ("client_ip", ""): "1.2.3.4", ...}.
+        A block by a gateway rule raises ParamFlowException whose rule is the converted ParamFlowRule and whose
+        rule_limit_app is String.valueOf of the parsed value ("$NM" for a value that missed its pattern)."""
+        gw = getattr(self, "_gateway", None)
+        if gw is None:
+            raise ValueError("gateway_entry needs a GatewayRuleManager on this sentinel")
+        return self.entry(resource, now, args=tuple(gw.parse_one(resource, mode, request)), **kw)
+
     # ---- block attribution (LogSlot)
     _PARAM_TEXTS_MAX = 4096
 
@@ -1049,41 +1060,58 @@ class ParamFlowRuleManager:
 
     def load_rules(self, rules: List[ParamFlowRule]) -> int:
         self._rules = list(rules)
-        rules = [r for r in rules if r.resource in self.s.ids]
-        arr = (SgaParamRule * max(1, len(rules)))()
-        keep = []
-        for i, r in enumerate(rules):
-            a = arr[i]
-            a.resource = self.s.ids[r.resource]
-            a.grade = r.grade
-            a.count = r.count
-            a.control_behavior = r.control_behavior
-            a.max_queueing_time_ms = r.max_queueing_time_ms
-            a.burst_count = r.burst_count
-            a.param_idx = r.param_idx
-            a.duration_in_sec = r.duration_in_sec
-            if r.cluster_mode:  # ParamFlowRule.clusterMode + ParamFlowClusterConfig
-                cc = r.cluster_config
-                a.cluster_mode = 1
-                a.cluster_flow_id = cc.flow_id if cc and cc.flow_id is not None else 0
-                a.cluster_fallback = 1 if cc and cc.fallback_to_local_when_fail else 0
-                a.cluster_sample_count = cc.sample_count if cc else 0
-                a.cluster_window_ms = cc.window_interval_ms if cc else 0
-            # ParamFlowRuleUtil.parseHotItems: later items with the same value win
-            hot: Dict[int, int] = {}
-            for it in r.param_flow_item_list:
-                hot[param_value(it.object)] = int(it.count)
-            hv = (C.c_uint64 * max(1, len(hot)))(*hot.keys())
-            ht = (C.c_int32 * max(1, len(hot)))(*hot.values())
-            keep += [hv, ht]
-            a.n_hot = len(hot)
-            a.hot_values = C.cast(hv, C.POINTER(C.c_uint64))
-            a.hot_thresholds = C.cast(ht, C.POINTER(C.c_int32))
-        rc = _lib.load().sga_load_param_rules(self.s.engine.handle, arr, len(rules))
         if hasattr(self.s, "_loaded"):
-            self.s._loaded[Decision.BLOCK_PARAM] = rules
-        self._keep = keep
+            self.s._param_own = self._rules
+        rc, self._keep = _send_param_rules(self.s, self._rules)
         return check(rc, self.s.engine.handle, "ParamFlowRuleManager.loadRules")
+
+
+def _send_param_rules(s, own: List[ParamFlowRule]):
+    """sga_load_param_rules of a sentinel's effective parameter rule list: the converted rules of its
+    GatewayRuleManager (none without one) -- GatewayFlowSlot runs ahead of ParamFlowSlot -- then `own`, the list
+    last given to ParamFlowRuleManager.  Returns (rc, the arrays the call borrowed)."""
+    gw = getattr(s, "_gateway", None)
+    rules = (gw.converted_rules() if gw is not None else []) + list(own)
+    rules = [r for r in rules if r.resource in s.ids]
+    arr = (SgaParamRule * max(1, len(rules)))()
+    keep = []
+    for i, r in enumerate(rules):
+        a = arr[i]
+        a.resource = s.ids[r.resource]
+        a.grade = r.grade
+        a.count = r.count
+        a.control_behavior = r.control_behavior
+        a.max_queueing_time_ms = r.max_queueing_time_ms
+        a.burst_count = r.burst_count
+        a.param_idx = r.param_idx
+        a.duration_in_sec = r.duration_in_sec
+        if r.cluster_mode:  # ParamFlowRule.clusterMode + ParamFlowClusterConfig
+            cc = r.cluster_config
+            a.cluster_mode = 1
+            a.cluster_flow_id = cc.flow_id if cc and cc.flow_id is not None else 0
+            a.cluster_fallback = 1 if cc and cc.fallback_to_local_when_fail else 0
+            a.cluster_sample_count = cc.sample_count if cc else 0
+            a.cluster_window_ms = cc.window_interval_ms if cc else 0
+        # ParamFlowRuleUtil.parseHotItems: later items with the same value win
+        hot: Dict[int, int] = {}
+        for it in r.param_flow_item_list:
+            hot[param_value(it.object)] = int(it.count)
+        hv = (C.c_uint64 * max(1, len(hot)))(*hot.keys())
+        ht = (C.c_int32 * max(1, len(hot)))(*hot.values())
+        keep += [hv, ht]
+        a.n_hot = len(hot)
+        a.hot_values = C.cast(hv, C.POINTER(C.c_uint64))
+        a.hot_thresholds = C.cast(ht, C.POINTER(C.c_int32))
+    rc = _lib.load().sga_load_param_rules(s.engine.handle, arr, len(rules))
+    if hasattr(s, "_loaded"):
+        s._loaded[Decision.BLOCK_PARAM] = rules
+    return rc, keep
+
+
+def send_param_rules(s) -> int:
+    """Re-sends the effective list after the gateway rules changed (GatewayRuleManager.load_rules)."""
+    rc, s._param_keep = _send_param_rules(s, getattr(s, "_param_own", []))
+    return check(rc, s.engine.handle, "GatewayRuleManager.loadRules")
 
 
 class DegradeRuleManager:
