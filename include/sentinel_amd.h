@@ -985,12 +985,39 @@ int sga_gateway_load(sga_engine *e, const sga_gateway_item *items, size_t n_item
 int sga_gateway_max_args(sga_engine *e, uint32_t *out);
 /* XXH64(bytes, SGA_GW_SEED): the key sga_gateway_parse* give a string ("$NM" and "$D" included). */
 uint64_t sga_gateway_string_key(const uint8_t *bytes, size_t len);
+
+/* REGEX items decided on the device: a program is a DFA over the bytes of the value, compiled by the caller (the
+ * Python front end compiles Python's `re` dialect, sentinel_amd/gateway_regex.py; a front end that wants
+ * java.util.regex's answers compiles its own tables).  The kernel walks s = 1; for each byte
+ * s = trans[s * n_classes + class_map[byte]], leaving at s == 0; the value matches iff bit (s & 7) of
+ * accept[s >> 3] is set (the empty value is answered by state 1).  State 0 is dead: row 0 is all zeros and it does
+ * not accept.  item: an index into the item array of the last sga_gateway_load.  class_off (256 bytes), trans_off
+ * (n_states * n_classes uint16, row-major; a multiple of 2) and accept_off ((n_states + 7) / 8 bytes) point into
+ * the blob; programs may share slices. */
+typedef struct sga_gateway_regex {
+    uint32_t item;
+    uint32_t n_states, n_classes;
+    uint32_t class_off, trans_off, accept_off;
+} sga_gateway_regex;
+/* Attaches programs to the table last loaded (n_programs = 0 drops them all; sga_gateway_load drops them too: they
+ * belong to the table they were compiled for).  The slot a program's item writes is then decided by the program:
+ * its bit of the regex_bits word is ignored, and so is a NULL word.  An item shadowed by a later one on its index
+ * decides nothing, with or without a program; of two programs for one item the later counts.  Everything is
+ * checked on the host before anything is uploaded, so the walk needs no bounds checks: SGA_EINVAL, with the
+ * engine's programs left as they were, unless every program names a REGEX item with a pattern, has
+ * 2 <= n_states <= 65535 and 1 <= n_classes <= 256, slices inside the blob, an even trans_off, class values below
+ * n_classes, transitions below n_states, an all-zero row 0 and a state 0 that does not accept. */
+int sga_gateway_load_regex(sga_engine *e, const sga_gateway_regex *programs, size_t n_programs, const uint8_t *blob,
+                           size_t blob_len);
+/* How many argument slots are decided by a program. */
+int sga_gateway_regex_count(sga_engine *e, uint32_t *out);
 /* Over DEVICE buffers, asynchronous on `hip_stream` with the ordering of sga_submit_events_device; n <= max_batch.
  * d_mode[i]: the request's resource mode.  The values are read as aligned 4-byte words: d_bytes must be readable from
  * the 4-byte boundary at or below it to the one at or above d_bytes + n_bytes (any hipMalloc'd buffer is).
  *  Field k of event i is d_bytes[d_field_off[i * n_fields + k] ..
  * + d_field_len[i * n_fields + k]) (any offset, any length; SGA_GW_NULL: null).  d_regex_bits (may be NULL: every
- * REGEX item matches): bit `index` of word i = the REGEX item at that index matches event i's value.
+ * REGEX item matches): bit `index` of word i = the REGEX item at that index matches event i's value.  A REGEX item
+ * with a program (sga_gateway_load_regex, below) is matched on the device and reads no bit.
  * For every event whose resource has items: the SGA_EV_ARGS words of parseParameterFor's array go to
  * d_param_values[value_base + i * 2 * max_args ..), d_param[i] = offset << 32 | nargs, d_flags[i] |= SGA_EV_ARGS
  * (nargs 0 when a rule's resource mode differs from d_mode[i]).  Null fields and unwritten slots are

@@ -132,6 +132,11 @@ class SgaGatewayItem(C.Structure):  # sga_gateway_item: one valid GatewayFlowRul
                 ("has_pattern", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
+class SgaGatewayRegex(C.Structure):  # sga_gateway_regex: the DFA that decides one REGEX item on the device
+    _fields_ = [("item", C.c_uint32), ("n_states", C.c_uint32), ("n_classes", C.c_uint32), ("class_off", C.c_uint32),
+                ("trans_off", C.c_uint32), ("accept_off", C.c_uint32)]
+
+
 SGA_TAG_SCALAR, SGA_TAG_LIST = 0, 1  # sga_block_row.tag_kind
 
 SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
@@ -274,6 +279,8 @@ SIGNATURES = {
     "sga_gateway_load": (C.c_int, [C.c_void_p, C.POINTER(SgaGatewayItem), C.c_size_t, C.c_void_p, C.c_size_t,
                                    C.c_uint32]),
     "sga_gateway_max_args": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "sga_gateway_load_regex": (C.c_int, [C.c_void_p, C.POINTER(SgaGatewayRegex), C.c_size_t, C.c_void_p, C.c_size_t]),
+    "sga_gateway_regex_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "sga_gateway_string_key": (C.c_uint64, [C.c_void_p, C.c_size_t]),
     "sga_gateway_parse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,

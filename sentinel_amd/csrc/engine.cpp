@@ -2558,6 +2558,22 @@ int sga_gateway_load(sga_engine *e, const sga_gateway_item *items, size_t n_item
     });
 }
 
+int sga_gateway_load_regex(sga_engine *e, const sga_gateway_regex *programs, size_t n_programs, const uint8_t *blob,
+                           size_t blob_len) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.gateway.load_regex(programs, n_programs, blob, blob_len, g.stream);
+    });
+}
+
+int sga_gateway_regex_count(sga_engine *e, uint32_t *out) {
+    if (!out) return SGA_EINVAL;
+    return guarded(e, [&](Engine &g) {
+        *out = g.gateway.n_regex_slots;
+        return SGA_OK;
+    });
+}
+
 int sga_gateway_max_args(sga_engine *e, uint32_t *out) {
     if (!out) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {

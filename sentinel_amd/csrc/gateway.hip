@@ -2,7 +2,9 @@
 #include "gateway.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cstring>
+#include <map>
 
 namespace sga {
 
@@ -67,6 +69,34 @@ __device__ __forceinline__ bool bytes_contain(const uint8_t *v, uint32_t vn, con
     return false;
 }
 
+// A REGEX program over the value: s = 1; per byte s = trans[s * n_classes + class_map[byte]] until s == 0 (the dead
+// state); the accept bit of s answers, for an empty value that of the start state.  The value is read as the aligned
+// dwords that hold a byte of it, one load for up to four bytes (Guideline 13, as DevRd does for the hash; the
+// tables' own bytes and halfwords are what they are).  load_regex checked every class and transition against the
+// table's sizes, so whatever the bytes -- malformed UTF-8 included -- the walk stays inside the tables.
+__device__ __forceinline__ bool regex_walk(const GwRegex P, const uint8_t *__restrict__ blob, const uint8_t *v,
+                                           uint32_t len) {
+    const uint8_t *cls = blob + P.class_off;
+    const uint16_t *trans = (const uint16_t *)(blob + P.trans_off);
+    const DevRd rd(v);
+    const uint32_t *w = rd.base;
+    uint32_t s = 1, word = 0, have = 0;  // have: bytes of the value left in word
+    if (len) {
+        word = *w >> rd.sh;
+        have = 4 - (rd.sh >> 3);
+    }
+    for (uint32_t left = len; left && s; --left) {
+        if (have == 0) {
+            word = *++w;
+            have = 4;
+        }
+        s = trans[s * P.n_classes + cls[word & 0xFFu]];
+        word >>= 8;
+        --have;
+    }
+    return (blob[P.accept_off + (s >> 3)] >> (s & 7u)) & 1u;
+}
+
 // One lane per (event, argument slot).  Slot 0's lane also owns the event's flags and param words and checks
 // every slice of the event, so a refused event is poisoned by one writer; the other lanes check their own slice
 // and the event's room again and write nothing when either fails.
@@ -123,7 +153,9 @@ __global__ __launch_bounds__(kT) void k_gateway_parse(GwTable t, const uint32_t 
                 const uint8_t *p = t.pat + S.pat_off;
                 if (S.match == SGA_GW_EXACT) keep = fl == S.pat_len && bytes_equal(v, p, fl);
                 else if (S.match == SGA_GW_CONTAINS) keep = bytes_contain(v, fl, p, S.pat_len);
-                else if (S.match == SGA_GW_REGEX) keep = !regex_bits || ((regex_bits[i] >> k) & 1ull);
+                else if (S.match == SGA_GW_REGEX)  // a program goes before the word
+                    keep = S.program ? regex_walk(t.rx[S.pat_off], t.rx_blob, v, fl)
+                                     : !regex_bits || ((regex_bits[i] >> k) & 1ull);
             }
             key = keep ? xxh64(DevRd(v), fl, SGA_GW_SEED) : t.key_nm;
         }
@@ -171,6 +203,7 @@ int GatewayEngine::load(const sga_gateway_item *items, size_t n_items, const uin
         most = std::max(most, na);
     }
     std::vector<GwSlot> slots(total, GwSlot{0, 0, 0, kGwNull, 0, 0, 0});
+    std::vector<int64_t> winner(total, -1);  // the item that writes each slot
     for (uint32_t r = 0; r < nres_now; ++r)
         if (non_param[r]) slots[res[r].slot_off + res[r].nargs - 1].kind = kGwDefault;
     for (size_t j = 0; j < n_items; ++j) {
@@ -183,11 +216,26 @@ int GatewayEngine::load(const sga_gateway_item *items, size_t n_items, const uin
                               ? (uint8_t)it.match_strategy
                               : (uint8_t)1;
         S = GwSlot{it.field, it.pattern_off, it.pattern_len, kGwItem, m, (uint8_t)(it.has_pattern ? 1 : 0), 0};
+        winner[res[it.resource].slot_off + it.index] = (int64_t)j;
+    }
+    // the slot each REGEX item with a pattern decides (load_regex): -1 not such an item, -2 shadowed
+    std::vector<int32_t> rslot(n_items, -1);
+    for (size_t j = 0; j < n_items; ++j) {
+        const sga_gateway_item &it = items[j];
+        if (it.index < 0 || it.match_strategy != SGA_GW_REGEX || !it.has_pattern) continue;
+        const uint32_t q = res[it.resource].slot_off + it.index;
+        rslot[j] = winner[q] == (int64_t)j ? (int32_t)q : -2;
     }
     // No parse in flight reads the old table: a parse on a caller stream ends with the engine stream waiting for
     // that stream (Engine::leave_stream), so the engine stream's end is past every parse issued so far.
     SGA_HIP_CHECK(hipStreamSynchronize(s));
     max_args = 0;
+    // the programs belonged to the table that goes
+    d_rx.release();
+    d_rx_blob.release();
+    n_regex_slots = 0;
+    slots0.clear();
+    regex_slot.clear();
     if (!most) {
         d_res.release();
         d_slot.release();
@@ -206,6 +254,65 @@ int GatewayEngine::load(const sga_gateway_item *items, size_t n_items, const uin
     max_args = most;
     key_nm = gateway_string_key((const uint8_t *)"$NM", 3);
     key_d = gateway_string_key((const uint8_t *)"$D", 2);
+    slots0 = std::move(slots);
+    regex_slot = std::move(rslot);
+    return SGA_OK;
+}
+
+int GatewayEngine::load_regex(const sga_gateway_regex *programs, size_t n_programs, const uint8_t *blob,
+                              size_t blob_len, hipStream_t s) {
+    if (n_programs && (!programs || !blob)) return SGA_EINVAL;
+    if (blob_len > 0xFFFFFFFFull) return SGA_EINVAL;  // the offsets are 32 bits
+    std::vector<GwSlot> slots = slots0;
+    std::vector<GwRegex> recs;
+    std::map<std::array<uint32_t, 5>, uint32_t> seen;  // slices already checked -> their record
+    for (size_t j = 0; j < n_programs; ++j) {
+        const sga_gateway_regex &P = programs[j];
+        if (P.item >= regex_slot.size() || regex_slot[P.item] == -1) return SGA_EINVAL;
+        if (P.n_states < 2 || P.n_states > 65535 || P.n_classes < 1 || P.n_classes > 256) return SGA_EINVAL;
+        const uint64_t nt = (uint64_t)P.n_states * P.n_classes, na = (P.n_states + 7) / 8;
+        if ((uint64_t)P.class_off + 256 > blob_len || (uint64_t)P.trans_off + 2 * nt > blob_len ||
+            (uint64_t)P.accept_off + na > blob_len || (P.trans_off & 1u))
+            return SGA_EINVAL;
+        const std::array<uint32_t, 5> key{P.n_states, P.n_classes, P.class_off, P.trans_off, P.accept_off};
+        auto it = seen.find(key);
+        if (it == seen.end()) {
+            for (uint32_t b = 0; b < 256; ++b)
+                if (blob[P.class_off + b] >= P.n_classes) return SGA_EINVAL;
+            for (uint64_t q = 0; q < nt; ++q) {
+                uint16_t to;
+                std::memcpy(&to, blob + P.trans_off + 2 * q, 2);
+                if (to >= P.n_states || (q < P.n_classes && to != 0)) return SGA_EINVAL;  // row 0 is dead
+            }
+            if (blob[P.accept_off] & 1u) return SGA_EINVAL;  // state 0 accepts nothing
+            it = seen.emplace(key, (uint32_t)recs.size()).first;
+            recs.push_back(GwRegex{P.class_off, P.trans_off, P.accept_off, P.n_classes});
+        }
+        if (regex_slot[P.item] < 0) continue;  // shadowed: checked, decides nothing
+        GwSlot &S = slots[(size_t)regex_slot[P.item]];
+        S.program = 1;
+        S.pat_off = it->second;
+    }
+    uint32_t count = 0;
+    for (const GwSlot &S : slots) count += S.program;
+    // as in load(): the engine stream's end is past every parse issued so far
+    SGA_HIP_CHECK(hipStreamSynchronize(s));
+    if (!count) {
+        if (d_rx.p && d_slot.p)
+            SGA_HIP_CHECK(hipMemcpyAsync(d_slot.p, slots0.data(), slots0.size() * sizeof(GwSlot), hipMemcpyHostToDevice, s));
+        SGA_HIP_CHECK(hipStreamSynchronize(s));
+        d_rx.release();
+        d_rx_blob.release();
+        n_regex_slots = 0;
+        return SGA_OK;
+    }
+    d_rx.alloc(recs.size());
+    d_rx_blob.alloc(std::max<size_t>(blob_len, 4));
+    SGA_HIP_CHECK(hipMemcpyAsync(d_rx.p, recs.data(), recs.size() * sizeof(GwRegex), hipMemcpyHostToDevice, s));
+    SGA_HIP_CHECK(hipMemcpyAsync(d_rx_blob.p, blob, blob_len, hipMemcpyHostToDevice, s));
+    SGA_HIP_CHECK(hipMemcpyAsync(d_slot.p, slots.data(), slots.size() * sizeof(GwSlot), hipMemcpyHostToDevice, s));
+    SGA_HIP_CHECK(hipStreamSynchronize(s));
+    n_regex_slots = count;
     return SGA_OK;
 }
 

@@ -62,10 +62,16 @@ struct GwRes {
 };
 enum : uint8_t { kGwItem = 0, kGwNull = 1, kGwDefault = 2 };
 // One argument slot: the item that writes it (the last in load order among those sharing the index), none
-// (kGwNull: the slot stays null), or the "$D" constant (kGwDefault).
+// (kGwNull: the slot stays null), or the "$D" constant (kGwDefault).  program != 0: a REGEX slot decided on the
+// device; pat_off is then its index into GwTable::rx (the kernel never reads a REGEX slot's pattern bytes).
 struct GwSlot {
     uint32_t field, pat_off, pat_len;
-    uint8_t kind, match, has_pattern, pad;
+    uint8_t kind, match, has_pattern, program;
+};
+// One REGEX program (sga_gateway_regex, checked by GatewayEngine::load_regex): byte offsets into GwTable::rx_blob of
+// the 256-byte class map, the n_states x n_classes uint16 transitions (even) and the accept bits.
+struct GwRegex {
+    uint32_t class_off, trans_off, accept_off, n_classes;
 };
 struct GwTable {
     const GwRes *res;
@@ -73,6 +79,8 @@ struct GwTable {
     const uint8_t *pat;
     uint32_t nres, n_fields, max_args;
     uint64_t key_nm, key_d;  // "$NM", "$D"
+    const GwRegex *rx;       // null unless programs are loaded
+    const uint8_t *rx_blob;
 };
 
 struct GatewayEngine {
@@ -82,9 +90,21 @@ struct GatewayEngine {
     uint32_t nres = 0, n_fields = 0, max_args = 0;
     uint64_t key_nm = 0, key_d = 0;
     bool loaded() const { return max_args != 0; }
-    GwTable table() const { return GwTable{d_res.p, d_slot.p, d_pat.p, nres, n_fields, max_args, key_nm, key_d}; }
+    GwTable table() const {
+        return GwTable{d_res.p, d_slot.p, d_pat.p, nres, n_fields, max_args, key_nm, key_d, d_rx.p, d_rx_blob.p};
+    }
     int load(const sga_gateway_item *items, size_t n_items, const uint8_t *blob, size_t blob_len, uint32_t n_fields,
              uint32_t nres, hipStream_t s, std::string *err);
+    // REGEX programs of the loaded table (sga_gateway_load_regex).  The host keeps the slots as load() made them
+    // and, per item, the slot it won if it is a REGEX item with a pattern (-1 otherwise): attaching programs patches
+    // a copy and uploads it, dropping them uploads the original.
+    DevBuf<GwRegex> d_rx;
+    DevBuf<uint8_t> d_rx_blob;
+    std::vector<GwSlot> slots0;
+    std::vector<int32_t> regex_slot;  // per item of the last load; -2: a REGEX item a later item shadows
+    uint32_t n_regex_slots = 0;
+    int load_regex(const sga_gateway_regex *programs, size_t n_programs, const uint8_t *blob, size_t blob_len,
+                   hipStream_t s);
     // one launch over n events x max_args slots; status: a device word, bit 0 set for a refused event; bias: the
     // offset d_values[0] has in the caller's numbering (0 unless d_values is a chunk's staging buffer)
     void launch(const uint32_t *d_resource, const uint8_t *d_mode, const uint32_t *d_field_off,

@@ -22,7 +22,9 @@ table loaded through the C ABI with two items on one index, which the manager ne
 writes the slot (the later one).  REGEX patterns are evaluated on the host with
 Python's `re` (re.fullmatch for Matcher.matches); the Java and Python dialects differ in places (possessive
 quantifiers before Python 3.11, \\p{...} classes, inline-flag placement): a pattern Python cannot compile matches
-everything, as a pattern Java cannot compile does in the reference.
+everything, as a pattern Java cannot compile does in the reference.  A manager built with device_regex=True
+compiles the patterns of a regular subset into byte DFAs (gateway_regex.py) that the parse kernel walks; those
+items need no host pass and no regex_bits word, the rest keep it item by item.
 """
 import ctypes as C
 import re
@@ -31,8 +33,8 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
-from ._lib import SgaGatewayItem, check
+from . import _lib, gateway_regex
+from ._lib import SgaGatewayItem, SgaGatewayRegex, check
 from .rules import ParamFlowItem, ParamFlowRule, RuleConstant
 
 RESOURCE_MODE_ROUTE_ID = 0
@@ -230,9 +232,16 @@ class GatewayRuleManager:
     parameter rule list -- the converted gateway rules, in the order their resources first appear, then the rules
     last given to ParamFlowRuleManager -- and loads the parser's table (sga_gateway_load)."""
 
-    def __init__(self, sentinel):
+    def __init__(self, sentinel, device_regex: bool = False, regex_max_states: int = gateway_regex.MAX_STATES,
+                 regex_max_table_bytes: int = gateway_regex.MAX_TABLE_BYTES):
+        """device_regex: compile every REGEX item's pattern into a byte DFA at load_rules (gateway_regex.compile_dfa
+        under the two caps) and have the parse kernel decide it; the items the compiler declines stay on the
+        regex_bits word (regex_host_items).  False: every REGEX item follows the word, as a front end fills it."""
         self.s = sentinel
         sentinel._gateway = self
+        self.device_regex = bool(device_regex)
+        self.regex_max_states, self.regex_max_table_bytes = regex_max_states, regex_max_table_bytes
+        self._sent = None  # what the engine's table was loaded from: put back when a program load is refused
         self._rules: List[GatewayFlowRule] = []
         self._rule_map: Dict[str, List[GatewayFlowRule]] = {}
         self._converted: Dict[str, List[ParamFlowRule]] = {}
@@ -311,8 +320,20 @@ class GatewayRuleManager:
                 blob += pb
         # the table first: a refused table leaves the manager, the engine's table and its parameter rules as they were
         pat = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
-        check(_lib.load().sga_gateway_load(self.s.engine.handle, arr, len(items), pat, len(blob), len(fields)),
-              self.s.engine.handle, "GatewayRuleManager.loadRules")
+        table = (arr, len(items), pat, len(blob), len(fields))
+        programs = self._compile_programs(items) if self.device_regex else None
+        L, h = _lib.load(), self.s.engine.handle
+        check(L.sga_gateway_load(h, *table), h, "GatewayRuleManager.loadRules")
+        if programs is not None and programs[1]:
+            rc = L.sga_gateway_load_regex(h, *programs[:4])
+            if rc < 0:  # the engine goes back to the table the manager still describes
+                old_table, old_programs = self._sent or (((SgaGatewayItem * 1)(), 0, None, 0, 0), None)
+                L.sga_gateway_load(h, *old_table)
+                if old_programs is not None and old_programs[1]:
+                    L.sga_gateway_load_regex(h, *old_programs[:4])
+                check(rc, h, "GatewayRuleManager.loadRules (REGEX programs)")
+        self._sent = (table, programs)
+        on_device = programs[4] if programs is not None else set()
         self._rules, self._rule_map, self._converted = rules, rule_map, converted
         self._fields, self._slots = fields, slots
         from .local import send_param_rules
@@ -320,8 +341,46 @@ class GatewayRuleManager:
         self.max_args = max((len(v) for v in slots.values()), default=0)
         self._regex = {id(it): _compile(it.pattern) for row in slots.values() for e in row
                        if isinstance(e, tuple) for it in [e[1]]
-                       if it.pattern and it.match_strategy == PARAM_MATCH_STRATEGY_REGEX}
+                       if it.pattern and it.match_strategy == PARAM_MATCH_STRATEGY_REGEX and id(it) not in on_device}
         return len(self.get_rules())
+
+    def _compile_programs(self, items):
+        """The arguments of sga_gateway_load_regex for a table's items -- (programs, n, blob, blob_len) -- and the
+        ids of the items they decide.  One table per distinct pattern: items that share a pattern share its slices."""
+        dfas: Dict[str, object] = {}
+        where: Dict[str, Tuple[int, int, int]] = {}
+        blob = bytearray()
+        rows, on_device = [], set()
+        for j, (rid, r, col) in enumerate(items):
+            it = r.param_item
+            if col is None or not it.pattern or it.match_strategy != PARAM_MATCH_STRATEGY_REGEX:
+                continue
+            if it.pattern not in dfas:
+                dfas[it.pattern] = d = gateway_regex.compile_dfa(it.pattern, max_states=self.regex_max_states,
+                                                                 max_table_bytes=self.regex_max_table_bytes)
+                if d is not None:
+                    blob += b"\0" * (len(blob) & 1)
+                    t_off = len(blob)
+                    blob += d.trans.tobytes()
+                    where[it.pattern] = (len(blob), t_off, len(blob) + 256)
+                    blob += d.class_map.tobytes() + d.accept.tobytes()
+            d = dfas[it.pattern]
+            if d is None:
+                continue
+            rows.append((j, d.n_states, d.n_classes) + where[it.pattern])
+            on_device.add(id(it))
+        arr = (SgaGatewayRegex * max(1, len(rows)))()
+        for a, row in zip(arr, rows):
+            a.item, a.n_states, a.n_classes, a.class_off, a.trans_off, a.accept_off = row
+        buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
+        return arr, len(rows), buf, len(blob), on_device
+
+    def regex_host_items(self) -> List[Tuple[str, int, str]]:
+        """(resource, index, pattern) of the REGEX items that follow the regex_bits word: all of them without
+        device_regex, with it those the compiler declined.  Empty: parse_device needs no regex_bits."""
+        names = {rid: name for name, rid in self.s.ids.items()}
+        return [(names[rid], e[1].index, e[1].pattern) for rid, row in self._slots.items() for e in row
+                if isinstance(e, tuple) and id(e[1]) in self._regex]
 
     # ---- one request on the host (gateway_entry)
     def parse_one(self, resource: str, mode: int, request: Mapping) -> list:
@@ -342,7 +401,8 @@ class GatewayRuleManager:
     # ---- batches on the device
     def regex_bits(self, resources, requests) -> Optional[np.ndarray]:
         """One uint64 per event: bit k = the REGEX item that writes slot k matches the event's value (re.fullmatch;
-        a pattern that does not compile matches).  None when no loaded rule is a REGEX rule."""
+        a pattern that does not compile matches).  Bits are set for the items of regex_host_items only -- an item
+        the device decides has none, the kernel ignores its bit; None when there is no such item."""
         if not self._regex:
             return None
         bits = np.zeros(len(requests), dtype=np.uint64)
