@@ -1038,6 +1038,67 @@ int sga_gateway_parse(sga_engine *e, const uint32_t *resource, const uint8_t *mo
                       size_t n, uint8_t *flags, uint64_t *param, uint64_t *param_values, size_t n_values,
                       size_t value_base);
 
+/* ---- gateway API groups: request paths -> matching ApiDefinitions -> entries (new entry points only) ----
+ * What every adapter's filter does per request (pickMatchingApiDefinitions: the path against every loaded
+ * ApiDefinition, GW/api/matcher/AbstractApiMatcher.java; then one entry per matching API name with
+ * RESOURCE_MODE_CUSTOM_API_NAME) for a whole batch.  The table is a list of predicates; API k matches a request iff
+ * any predicate with api == k does.  kind EXACT: the path equals blob[a .. a + b).  kind DFA: a byte DFA walked over
+ * the path, a = n_states, b = n_classes, c = class_off, d = trans_off, e = accept_off -- sga_gateway_regex's format and
+ * contract (REGEX patterns, and Ant path patterns translated to the same tables by the front end).  kind HOST: bit a
+ * (< 64) of the request's host word, for what the front end decides itself. */
+typedef struct sga_gateway_api_pred {
+    uint32_t api;  /* < n_apis */
+    uint32_t kind; /* SGA_GW_API_* */
+    uint32_t a, b, c, d, e;
+} sga_gateway_api_pred;
+#define SGA_GW_API_EXACT 0
+#define SGA_GW_API_DFA 1
+#define SGA_GW_API_HOST 2
+#define SGA_GW_API_MAX 4096 /* design limit: APIs per table (64 bitmap words per request) */
+
+/* Replaces the table (n_preds = 0 clears it: the match and expand entries then launch nothing).  After
+ * sga_flow_set_resources.  api_resource[k] (< the resource count): the resource id API k is entered as.  Everything
+ * is checked on the host before anything is uploaded, so the walk carries no bounds checks.  SGA_EINVAL, with the
+ * loaded table left in place: an api >= n_apis, a resource out of range, an unknown kind, a slice outside the blob,
+ * a DFA that breaks sga_gateway_load_regex's rules, a host bit >= 64, n_apis = 0.  SGA_ERANGE, likewise: more than
+ * 64 HOST predicates, more than SGA_GW_API_MAX APIs. */
+int sga_gateway_api_load(sga_engine *e, const sga_gateway_api_pred *preds, size_t n_preds,
+                         const uint32_t *api_resource, size_t n_apis, const uint8_t *blob, size_t blob_len);
+/* The loaded table's API count (0: no table) and the predicates decided on the device (EXACT and DFA). */
+int sga_gateway_api_count(sga_engine *e, uint32_t *n_apis, uint32_t *n_device_preds);
+/* Over DEVICE buffers, asynchronous on `hip_stream` with the ordering of sga_submit_events_device; n <= max_batch.
+ * Request i's path is d_bytes[d_path_off[i] .. + d_path_len[i]) (SGA_GW_NULL: no path -- matches nothing), read as
+ * aligned 4-byte words under sga_gateway_parse_device's contract.  d_host_bits (may be NULL: every HOST predicate
+ * answers no match -- a missing answer must not enter a resource): one word per request.  d_match: n x W uint64,
+ * W = (n_apis + 63) / 64, bit k % 64 of word k / 64 of row i = API k matches request i; every row is written in full.
+ * A path slice that leaves the blob zeroes its row and sga_events_device_status reports SGA_EINVAL. */
+int sga_gateway_api_match_device(sga_engine *e, const uint32_t *d_path_off, const uint32_t *d_path_len,
+                                 const uint8_t *d_bytes, size_t n_bytes, const uint64_t *d_host_bits, size_t n,
+                                 uint64_t *d_match, void *hip_stream);
+/* The entry list of a batch, same ordering and n <= max_batch: request i contributes, in input order, the route entry
+ * (resource d_route[i], mode 0) unless d_route[i] == SGA_GW_NULL, then one entry per set bit of its row in ascending
+ * API index (resource api_resource[k], mode 1; the reference collects a HashSet: the order among one request's APIs
+ * is parity-unpinned).  Entry j: d_src[j] = its request, d_pos[j] = its position inside the request (a caller that
+ * wants the filter's stop-at-first-block submits position 0 of every request, then position 1 of the unblocked ones,
+ * and so on: that loop is the caller's).  d_field_off / d_field_len (n x n_fields) with the two _out arrays
+ * (cap x n_fields), all four or none: entry j gets row d_src[j] of the request field table, ready for
+ * sga_gateway_parse_device.  *d_total (uint32, device) = the entries needed; entries at or past cap are not written.
+ * SGA_ERANGE: n * (1 + n_apis) >= 2^32. */
+int sga_gateway_api_expand_device(sga_engine *e, const uint32_t *d_route, const uint64_t *d_match, size_t n,
+                                  const uint32_t *d_field_off, const uint32_t *d_field_len, uint32_t n_fields,
+                                  size_t cap, uint32_t *d_src, uint32_t *d_pos, uint32_t *d_resource, uint8_t *d_mode,
+                                  uint32_t *d_field_off_out, uint32_t *d_field_len_out, uint32_t *d_total,
+                                  void *hip_stream);
+/* The same over HOST buffers, synchronous, any n (chunks of max_batch inside, entry offsets continued across
+ * chunks).  sga_gateway_api_match: SGA_EINVAL for what the device form reports through the status call.
+ * sga_gateway_api_expand: *total = the entries needed; SGA_ERANGE when cap is smaller (the first cap are written). */
+int sga_gateway_api_match(sga_engine *e, const uint32_t *path_off, const uint32_t *path_len, const uint8_t *bytes,
+                          size_t n_bytes, const uint64_t *host_bits, size_t n, uint64_t *match);
+int sga_gateway_api_expand(sga_engine *e, const uint32_t *route, const uint64_t *match, size_t n,
+                           const uint32_t *field_off, const uint32_t *field_len, uint32_t n_fields, size_t cap,
+                           uint32_t *src, uint32_t *pos, uint32_t *resource, uint8_t *mode, uint32_t *field_off_out,
+                           uint32_t *field_len_out, size_t *total);
+
 /* Optional helper for tools: HIP stream of the engine (hipStream_t as void*). */
 void *sga_engine_stream(sga_engine *e);
 

@@ -6,5 +6,6 @@ host-side mirror of the reference's Java interface for that path.
 """
 from ._lib import EngineError, LIB_PATH  # noqa: F401
 from .gateway import GatewayFlowRule, GatewayParamFlowItem, GatewayRuleManager  # noqa: F401
+from .gateway_api import ApiDefinition, ApiPathPredicateItem, GatewayApiDefinitionManager  # noqa: F401
 
 __all__ = ["EngineError", "LIB_PATH", "GatewayFlowRule", "GatewayParamFlowItem", "GatewayRuleManager"]

@@ -137,6 +137,14 @@ class SgaGatewayRegex(C.Structure):  # sga_gateway_regex: the DFA that decides o
                 ("trans_off", C.c_uint32), ("accept_off", C.c_uint32)]
 
 
+class SgaGatewayApiPred(C.Structure):  # sga_gateway_api_pred: one path predicate of the API table
+    _fields_ = [("api", C.c_uint32), ("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("c", C.c_uint32),
+                ("d", C.c_uint32), ("e", C.c_uint32)]
+
+
+SGA_GW_API_EXACT, SGA_GW_API_DFA, SGA_GW_API_HOST = 0, 1, 2  # sga_gateway_api_pred.kind
+SGA_GW_API_MAX = 4096
+
 SGA_TAG_SCALAR, SGA_TAG_LIST = 0, 1  # sga_block_row.tag_kind
 
 SGA_PARENT_ENTRANCE = 0xFFFFFFFF  # sga_tree_row.parent / a parent array's "outermost": under the EntranceNode
@@ -288,6 +296,17 @@ SIGNATURES = {
     "sga_gateway_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_size_t]),
+    "sga_gateway_api_load": (C.c_int, [C.c_void_p, C.POINTER(SgaGatewayApiPred), C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_size_t]),
+    "sga_gateway_api_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "sga_gateway_api_match_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sga_gateway_api_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                C.c_uint32, C.c_size_t] + [C.c_void_p] * 8),
+    "sga_gateway_api_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "sga_gateway_api_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_uint32, C.c_size_t] + [C.c_void_p] * 6 + [C.POINTER(C.c_size_t)]),
     "sga_metrics_snapshot": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_cluster_metric_nodes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sga_wire_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(SgaWireBatch)]),

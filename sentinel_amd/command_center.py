@@ -25,6 +25,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 from urllib.parse import unquote_plus
 
 from .gateway import GatewayFlowRule, GatewayParamFlowItem
+from .gateway_api import ApiDefinition, ApiPathPredicateItem
 from .javautil import double_to_string, is_blank
 from .local import ENTRY_NODE, MetricNode, NodeView, SystemRule
 from .rules import (AuthorityRule, ClusterFlowConfig, DegradeRule, FlowRule, ParamFlowClusterConfig, ParamFlowItem,
@@ -224,7 +225,8 @@ def _camel(name: str) -> str:
 
 _NESTED = {(FlowRule, "cluster_config"): ClusterFlowConfig, (ParamFlowRule, "cluster_config"): ParamFlowClusterConfig,
            (ParamFlowRule, "param_flow_item_list"): ParamFlowItem,
-           (GatewayFlowRule, "param_item"): GatewayParamFlowItem}
+           (GatewayFlowRule, "param_item"): GatewayParamFlowItem,
+           (ApiDefinition, "predicate_items"): ApiPathPredicateItem}
 
 
 def rule_to_bean(rule) -> dict:
@@ -418,6 +420,10 @@ class CommandCenter:
         if "gateway" in self.managers:  # a gateway.GatewayRuleManager: the api-gateway adapter's two handlers
             self.register("gateway/getRules", "Fetch all gateway rules", self._gateway_get_rules)
             self.register("gateway/updateRules", "Update gateway rules", self._gateway_update_rules)
+        if "gateway_api" in self.managers:  # a gateway_api.GatewayApiDefinitionManager: the API group handlers
+            self.register("gateway/getApiDefinitions", "Fetch all customized gateway API groups",
+                          self._gateway_get_api_definitions)
+            self.register("gateway/updateApiDefinitions", "", self._gateway_update_api_definitions)
         self.new_id: Callable[[], object] = uuid.uuid4  # NodeVo's UUID.randomUUID()
 
     def register(self, name: str, desc: str, fn: Callable[[Dict[str, str]], str]) -> None:
@@ -505,6 +511,31 @@ class CommandCenter:
         if any(isinstance(o, dict) and o.get("clusterMode") for o in (arr or [])):
             raise ValueError("cluster-mode gateway rules do not exist in the reference: refused")
         self.managers["gateway"].load_rules(rules)
+        return "success"
+
+    def _gateway_get_api_definitions(self, p):
+        """GetGatewayApiDefinitionGroupCommandHandler: JSON.toJSONString(GatewayApiDefinitionManager.getApiDefinitions())."""
+        return to_json([rule_to_bean(d) for d in self.managers["gateway_api"].get_api_definitions()])
+
+    def _gateway_update_api_definitions(self, p):
+        """UpdateGatewayApiDefinitionGroupCommandHandler (:47-96): a blank data is "Bad data", data that does not
+        decode or parse "decode gateway API definition data error"; every element becomes an ApiDefinition whose
+        predicateItems are ApiPathPredicateItems (a missing array: an empty set).  The write-data-source branch is
+        not served."""
+        data = p.get("data")
+        if data is None or not data.strip():
+            raise ValueError("Bad data")
+        try:
+            arr = json.loads(unquote_plus(data, encoding="utf-8", errors="strict"))
+            defs = []
+            for o in arr:
+                d = rule_from_bean(ApiDefinition, o)
+                if d.predicate_items is None:
+                    d.predicate_items = []
+                defs.append(d)
+        except (ValueError, TypeError):
+            raise ValueError("decode gateway API definition data error")
+        self.managers["gateway_api"].load_api_definitions(defs)
         return "success"
 
     def _cluster_node(self, p):

@@ -6,6 +6,7 @@
 #include "concurrent.hpp"
 #include "flow.hpp"
 #include "gateway.hpp"
+#include "gateway_api.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -589,6 +590,7 @@ struct Engine {
     // ---- local flow engine
     FlowEngine flow;
     sga::GatewayEngine gateway;  // sga_gateway_*: request fields -> argument vectors, ahead of any submit entry
+    sga::GatewayApiEngine gateway_api;  // sga_gateway_api_*: request paths -> matching API groups -> entries
 
     int32_t uni_S = 0, uni_W = 0, uni_iv = 0;  // ClusterState::uni_S (sync_device)
     // pset 1: the second pipelined scratch set's dense table
@@ -2624,6 +2626,108 @@ int sga_gateway_parse(sga_engine *e, const uint32_t *resource, const uint8_t *mo
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
         return g.gateway.parse_host(resource, mode, field_off, field_len, bytes, n_bytes, regex_bits, n, flags, param,
                                     param_values, n_values, value_base, g.cfg.max_batch, g.stream);
+    });
+}
+
+int sga_gateway_api_load(sga_engine *e, const sga_gateway_api_pred *preds, size_t n_preds,
+                         const uint32_t *api_resource, size_t n_apis, const uint8_t *blob, size_t blob_len) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.gateway_api.load(preds, n_preds, api_resource, n_apis, blob, blob_len, g.flow.nres, g.stream, &g.err);
+    });
+}
+
+int sga_gateway_api_count(sga_engine *e, uint32_t *n_apis, uint32_t *n_device_preds) {
+    if (!n_apis || !n_device_preds) return SGA_EINVAL;
+    return guarded(e, [&](Engine &g) {
+        *n_apis = g.gateway_api.n_apis;
+        *n_device_preds = g.gateway_api.n_device_preds;
+        return SGA_OK;
+    });
+}
+
+int sga_gateway_api_match_device(sga_engine *e, const uint32_t *d_path_off, const uint32_t *d_path_len,
+                                 const uint8_t *d_bytes, size_t n_bytes, const uint64_t *d_host_bits, size_t n,
+                                 uint64_t *d_match, void *hip_stream) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway_api.loaded() || n == 0) return SGA_OK;  // no table: nothing is launched
+        if (n > g.cfg.max_batch) return SGA_ERANGE;
+        if (!d_path_off || !d_path_len || !d_match || (n_bytes && !d_bytes)) return SGA_EINVAL;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        if (!g.flow.d_gate.p) {  // the device entry's status words (FlowEngine::device_status)
+            g.flow.d_gate.alloc(2);
+            SGA_HIP_CHECK(hipMemsetAsync(g.flow.d_gate.p, 0, 8, g.stream));
+        }
+        hipStream_t s = g.enter_stream(hip_stream);
+        g.gateway_api.launch_match(d_path_off, d_path_len, d_bytes, n_bytes, d_host_bits, (uint32_t)n, d_match,
+                                   g.flow.d_gate.p + 1, s);
+        g.leave_stream(s);
+        return SGA_OK;
+    });
+}
+
+int sga_gateway_api_match(sga_engine *e, const uint32_t *path_off, const uint32_t *path_len, const uint8_t *bytes,
+                          size_t n_bytes, const uint64_t *host_bits, size_t n, uint64_t *match) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway_api.loaded() || n == 0) return SGA_OK;
+        if (!path_off || !path_len || !match || (n_bytes && !bytes)) return SGA_EINVAL;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.gateway_api.match_host(path_off, path_len, bytes, n_bytes, host_bits, n, match, g.cfg.max_batch,
+                                        g.stream);
+    });
+}
+
+// what both expand entries refuse
+static int api_expand_args(const sga::GatewayApiEngine &a, size_t n, const void *route, const void *match,
+                           const void *fo, const void *fl, uint32_t n_fields, const void *src, const void *pos,
+                           const void *resource, const void *mode, const void *fo_out, const void *fl_out,
+                           const void *total) {
+    if (!route || !match || !src || !pos || !resource || !mode || !total) return SGA_EINVAL;
+    const int given = (fo != nullptr) + (fl != nullptr) + (fo_out != nullptr) + (fl_out != nullptr);
+    if ((given != 0 && given != 4) || (given == 4 && n_fields == 0)) return SGA_EINVAL;
+    if ((uint64_t)n * (1ull + a.n_apis) >= 0xFFFFFFFFull) return SGA_ERANGE;  // the scan and the indices are 32 bits
+    return SGA_OK;
+}
+
+int sga_gateway_api_expand_device(sga_engine *e, const uint32_t *d_route, const uint64_t *d_match, size_t n,
+                                  const uint32_t *d_field_off, const uint32_t *d_field_len, uint32_t n_fields,
+                                  size_t cap, uint32_t *d_src, uint32_t *d_pos, uint32_t *d_resource, uint8_t *d_mode,
+                                  uint32_t *d_field_off_out, uint32_t *d_field_len_out, uint32_t *d_total,
+                                  void *hip_stream) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway_api.loaded() || n == 0) return SGA_OK;  // no table: nothing is launched
+        if (n > g.cfg.max_batch) return SGA_ERANGE;
+        if (const int rc = api_expand_args(g.gateway_api, n, d_route, d_match, d_field_off, d_field_len, n_fields, d_src,
+                                           d_pos, d_resource, d_mode, d_field_off_out, d_field_len_out, d_total))
+            return rc;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        g.gateway_api.ensure_scratch(g.cfg.max_batch);  // before a caller stream is ordered after the engine stream
+        if (!g.flow.d_gate.p) {  // sga_events_device_status waits for the engine stream only once the words exist
+            g.flow.d_gate.alloc(2);
+            SGA_HIP_CHECK(hipMemsetAsync(g.flow.d_gate.p, 0, 8, g.stream));
+        }
+        hipStream_t s = g.enter_stream(hip_stream);
+        g.gateway_api.launch_count_scan(d_route, d_match, (uint32_t)n, s);
+        g.gateway_api.launch_scatter(d_route, d_match, (uint32_t)n, d_field_off, d_field_len, n_fields, cap, 0, d_src,
+                                     d_pos, d_resource, d_mode, d_field_off_out, d_field_len_out, d_total, s);
+        g.leave_stream(s);
+        return SGA_OK;
+    });
+}
+
+int sga_gateway_api_expand(sga_engine *e, const uint32_t *route, const uint64_t *match, size_t n,
+                           const uint32_t *field_off, const uint32_t *field_len, uint32_t n_fields, size_t cap,
+                           uint32_t *src, uint32_t *pos, uint32_t *resource, uint8_t *mode, uint32_t *field_off_out,
+                           uint32_t *field_len_out, size_t *total) {
+    return guarded(e, [&](Engine &g) {
+        if (!g.gateway_api.loaded() || n == 0) return SGA_OK;
+        if (const int rc = api_expand_args(g.gateway_api, n, route, match, field_off, field_len, n_fields, src, pos,
+                                           resource, mode, field_off_out, field_len_out, total))
+            return rc;
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        g.gateway_api.ensure_scratch(g.cfg.max_batch);
+        return g.gateway_api.expand_host(route, match, n, field_off, field_len, n_fields, cap, src, pos, resource, mode,
+                                         field_off_out, field_len_out, total, g.cfg.max_batch, g.stream);
     });
 }
 

@@ -694,6 +694,26 @@ class LocalSentinel:
             raise ValueError("gateway_entry needs a GatewayRuleManager on this sentinel")
         return self.entry(resource, now, args=tuple(gw.parse_one(resource, mode, request)), **kw)
 
+    def gateway_request(self, route: Optional[str], path: Optional[str], request, now: int, **kw):
+        """A gateway filter's sequence for one request (SentinelZuulPreFilter.run:118-134 and its twins; a sentinel
+        with a gateway.GatewayRuleManager and a gateway_api.GatewayApiDefinitionManager): gateway_entry on the route
+        (mode 0) unless it is blank, then on every API group matching_apis_one(path) names (mode 1), in definition
+        order, stopping at the first block.  Returns (entries, block): the entries made, for the caller to exit, and
+        the BlockException that ended the sequence or None.  A matching definition whose name is no registered
+        resource is not entered."""
+        apis = getattr(self, "_gateway_api", None)
+        if apis is None:
+            raise ValueError("gateway_request needs a GatewayApiDefinitionManager on this sentinel")
+        todo = [] if route is None or not route.strip() else [(route, 0)]
+        todo += [(name, 1) for name in apis.matching_apis_one(path) if name in self.ids]
+        entries: List[Entry] = []
+        for name, mode in todo:
+            try:
+                entries.append(self.gateway_entry(name, mode, request, now, **kw))
+            except BlockException as e:
+                return entries, e
+        return entries, None
+
     # ---- block attribution (LogSlot)
     _PARAM_TEXTS_MAX = 4096
 

@@ -19,7 +19,16 @@ One JSON line.  The kernel's own time: rocprofv3 --kernel-trace --stats -- pytho
   device  a manager with device_regex=True: the kernel walks the pattern's DFA, no word is passed
   host    a default manager, the only way without programs: per step GatewayRuleManager.regex_bits over the 2^20
           requests on the host (2 timed passes), the upload of the word (5 timed), then the parse with the word
---skip-decide leaves the submit step out."""
+--skip-decide leaves the submit step out.
+
+--api device|global|host is another workload ("Gateway API groups"): 2^20 requests with paths of
+8 to 40 bytes against 64 API groups -- each an EXACT pattern and a /svcNN/** prefix, one of them a REGEX besides --
+and 16 routes:
+  device  sga_gateway_api_match_device and sga_gateway_api_expand_device (with the gather of a two-column field
+          table), each timed like the parse step; the table is staged in LDS
+  global  the same table behind a blob padded past the staging limit: the walk reads global memory (the A/B)
+  host    the only way without the table: matching_apis_one per request on the host, timed over --host-sample
+          requests of the same data (2^14 by default) and scaled to the batch"""
 import argparse
 import json
 import os
@@ -37,6 +46,123 @@ T0 = 1_700_000_000_000
 HBM_TBS = 8.0  # MI355X_MICROARCH.md, the figure of DESIGN.md section 3
 
 
+def api_main(opt):
+    import ctypes as C
+
+    import torch
+    from sentinel_amd import _lib
+    from sentinel_amd import gateway_api as A
+    n, n_api, n_route = 1 << opt.n_log2, 64, 16
+    rng = np.random.default_rng(2025)
+    names = [f"route{r}" for r in range(n_route)] + [f"svc{k:02d}" for k in range(n_api)]
+    eng = Engine(max_batch=n)
+    s = LocalSentinel(eng, names)
+    m = A.GatewayApiDefinitionManager(s)
+    defs = []
+    for k in range(n_api):
+        items = [A.ApiPathPredicateItem(f"/svc{k:02d}/health", 0), A.ApiPathPredicateItem(f"/svc{k:02d}/**", 1)]
+        if k == 7:
+            items.append(A.ApiPathPredicateItem(r"/user/\d+/orders(?:/\d+)?", 2))
+        defs.append(A.ApiDefinition(f"svc{k:02d}", items))
+    m.load_api_definitions(defs)
+    assert m.host_predicates() == [] and m.words == 1
+    # the paths with numpy: /svcNN/health, /svcNN/<8..30 bytes>, /user/<id>/orders[/<id>], and paths nobody claims
+    svc = np.char.add("/svc", np.char.zfill(rng.integers(0, n_api + 8, size=n).astype(str), 2))  # 8 of 72 unknown
+    tails = np.array(["/health", "/v1/items", "/v1/items/4711", "/v2/orders/2024/10/21/open", "/static/app.js",
+                      "/v1/customers/8812/address"])[rng.integers(0, 6, size=n)]
+    users = np.char.add(np.char.add("/user/", rng.integers(1, 10 ** 6, size=n).astype(str)),
+                        np.where(rng.random(n) < 0.5, "/orders", "/orders/77"))
+    paths = np.where(rng.random(n) < 0.1, users, np.char.add(svc, tails))
+    plen = np.char.str_len(paths).astype(np.uint32)
+    assert plen.min() >= 8 and plen.max() <= 40
+    off = np.concatenate([[0], np.cumsum(plen)[:-1]]).astype(np.uint32)
+    blob = np.frombuffer("".join(paths.tolist()).encode("ascii"), np.uint8)
+    routes = rng.integers(0, n_route + 1, size=n).astype(np.uint32)
+    routes[routes == n_route] = A.ROUTE_NULL
+    out = {"workload": "api", "mode": opt.api, "requests": n, "apis": n_api, "routes": n_route,
+           "blob_bytes": int(len(blob)), "hbm_gb_s": HBM_TBS * 1000}
+    if opt.api == "host":
+        k = min(n, opt.host_sample)
+        sample = paths[:k].tolist()
+        passes = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            hits = sum(len(m.matching_apis_one(v)) for v in sample)
+            passes.append((time.perf_counter() - t0) * 1e3)
+        out.update({"host_sample": k, "host_sample_ms_passes": [round(x, 1) for x in passes],
+                    "host_us_per_request": round(min(passes) * 1e3 / k, 2),
+                    "host_ms_scaled_to_batch": round(min(passes) * n / k, 1), "sample_matches": hits})
+        print(json.dumps(out), flush=True)
+        eng.close()
+        return
+    if opt.api == "global":  # the same predicates, the blob padded past kApiLdsBytes
+        arr, n_preds, res, buf, blob_len = m._sent
+        pad = (C.c_uint8 * (blob_len + 70000)).from_buffer_copy(bytes(buf[:blob_len]) + bytes(70000))
+        assert _lib.load().sga_gateway_api_load(eng.handle, arr, n_preds, res.ctypes.data, len(res), pad, len(pad)) == 0
+    dev = torch.device("cuda", eng.device)
+    t = lambda a: torch.from_numpy(np.array(a)).to(dev)  # noqa: E731
+    nf = 2
+    d_off, d_len, d_blob = t(off.view(np.int32)), t(plen.view(np.int32)), t(blob)
+    d_routes = t(routes.view(np.int32))
+    d_match = torch.zeros(n, dtype=torch.int64, device=dev)
+    d_fo, d_fl = t(rng.integers(0, 1 << 30, size=n * nf).astype(np.int32)), t(rng.integers(0, 40, size=n * nf).astype(np.int32))
+    cap = 3 * n
+    i32 = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)  # noqa: E731
+    src, pos, d_res, d_total = i32(cap), i32(cap), i32(cap), i32(1)
+    d_mode = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    fo_out, fl_out = i32(cap * nf), i32(cap * nf)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+
+    def match():
+        m.match_device(d_off, d_len, d_blob, d_match, stream=stream)
+
+    def expand():
+        m.expand_device(d_routes, d_match, cap, src, pos, d_res, d_mode, d_total, field_off=d_fo, field_len=d_fl,
+                        n_fields=nf, field_off_out=fo_out, field_len_out=fl_out, stream=stream)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        reps, rounds = 20, []
+        for _ in range(5):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            for _ in range(reps):
+                fn()
+            b.record(stream)
+            b.synchronize()
+            rounds.append(a.elapsed_time(b) / reps)
+        return rounds
+
+    mr = timed(match)
+    er = timed(expand)
+    s.device_status()
+    total = int(d_total.item())
+    rows = d_match.cpu().numpy().view(np.uint64)
+    matched = int((rows != 0).sum())
+    # a sample against the host model
+    for i in rng.integers(0, n, size=200).tolist():
+        want = m.matching_apis_one(str(paths[i]))
+        got = [m.columns()[k] for k in range(n_api) if (int(rows[i]) >> k) & 1]
+        assert got == want, (paths[i], got, want)
+    assert total == int((routes != A.ROUTE_NULL).sum()) + int(np.unpackbits(rows.view(np.uint8)).sum())
+    match_ms, expand_ms = float(np.median(mr)), float(np.median(er))
+    mb_r, mb_w = n * 8 + len(blob), n * 8
+    eb_r = n * 4 + n * 8 * 2 + n * 4 * 4 + total * nf * 8
+    eb_w = n * 4 * 2 + total * (4 + 4 + 4 + 1) + total * nf * 8
+    out.update({"in_lds": opt.api == "device", "requests_matching": matched, "entries": total,
+                "match_ms": round(match_ms, 4), "match_ms_rounds": [round(x, 4) for x in mr],
+                "match_bytes_read": int(mb_r), "match_bytes_written": int(mb_w),
+                "match_gb_s": round((mb_r + mb_w) / match_ms / 1e6, 1),
+                "expand_ms": round(expand_ms, 4), "expand_ms_rounds": [round(x, 4) for x in er],
+                "expand_bytes_read": int(eb_r), "expand_bytes_written": int(eb_w),
+                "expand_gb_s": round((eb_r + eb_w) / expand_ms / 1e6, 1)})
+    print(json.dumps(out), flush=True)
+    eng.close()
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -44,7 +170,11 @@ def main():
     ap.add_argument("--regex", choices=["device", "host"])
     ap.add_argument("--pattern", default=r"[a-z]+-\d{2,4}-gold")
     ap.add_argument("--skip-decide", action="store_true")
+    ap.add_argument("--api", choices=["device", "global", "host"])
+    ap.add_argument("--host-sample", type=int, default=1 << 14)
     opt = ap.parse_args()
+    if opt.api:
+        return api_main(opt)
     n = 1 << opt.n_log2
     n_res = 1024
     rng = np.random.default_rng(2024)
