@@ -855,6 +855,52 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
  * resource's rules: SGA_EINVAL. */
 int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index);
 
+/* ---- token server log (ClusterServerStatLogUtil; new entry points only) ---- */
+/* The cluster checkers record what they refused through ClusterServerStatLogUtil.log(msg[, count])
+ * (CS/flow/ClusterFlowChecker.java:91,102-107, ClusterParamFlowChecker.java:77-79, RLS SimpleClusterFlowChecker.java:49-61),
+ * which a StatLogger sums per second into sentinel-server.log.  The engine keeps those sums on the device: once
+ * enabled, every token batch of every entry (sga_request_tokens and its device, packed, async and pipelined forms,
+ * the coalescing queue, sga_request_param_tokens, sga_rls_should_rate_limit and its device form) ends with one pass
+ * that adds the batch's requests to an engine-resident table of rows.  One request forms one tuple or none:
+ *   SGA_SLOG_FLOW_BLOCK       BLOCKED, not prioritized (or an RLS descriptor)   count += acquire, events += 1
+ *   SGA_SLOG_FLOW_BLOCK_PRIO  BLOCKED, prioritized                              count += acquire, events += 1
+ *   SGA_SLOG_FLOW_WAITING     SHOULD_WAIT                                       count += 1,       events += 1
+ *   SGA_SLOG_FLOW_PASS        OK, RLS descriptors only                          count += acquire, events += 1
+ *   SGA_SLOG_PARAM_PASS       requestParamToken OK with a non-empty value list  count += 1,       events += 1
+ *   SGA_SLOG_PARAM_BLOCK      requestParamToken BLOCKED; tag = the first value  count += 1,       events += 1
+ *                             in collection order whose nextRemaining < 0
+ * Nothing is formed for TOO_MANY_REQUEST, FAIL, NO_RULE_EXISTS and BAD_REQUEST (an empty value list among them)
+ * nor for a batch that failed.  Off by default: an engine that never enables the log launches and allocates
+ * nothing for it. */
+#define SGA_SLOG_FLOW_BLOCK 0
+#define SGA_SLOG_FLOW_BLOCK_PRIO 1
+#define SGA_SLOG_FLOW_WAITING 2
+#define SGA_SLOG_FLOW_PASS 3
+#define SGA_SLOG_PARAM_PASS 4
+#define SGA_SLOG_PARAM_BLOCK 5
+typedef struct sga_server_log_row {   /* sizeof == 40 */
+    int64_t time_slot;   /* t - t % 1000 of the requests (StatLogger's rolling slot at intervalSeconds(1)) */
+    int64_t flow_id;
+    uint64_t tag;        /* SGA_SLOG_PARAM_BLOCK: the blocking value's 64-bit key; 0 for every other kind */
+    int64_t count;
+    uint32_t events;
+    uint8_t kind;        /* SGA_SLOG_* */
+    uint8_t reserved[3]; /* zero */
+} sga_server_log_row;
+
+/* Turns the log on with room for max_rows rows (0: the default of 65,536; at least 64; rounded up to a power of
+ * two; at most 2^26).  Two tuples whose 64-bit hashes collide share a row, as in the block log.  Calling it again
+ * resizes an empty log; with rows pending: SGA_EINVAL. */
+int sga_server_log_enable(sga_engine *e, uint32_t max_rows);
+
+/* Moves out every row with time_slot + 1000 <= before_ms (INT64_MAX: all), sorted by (time_slot, flow_id, kind,
+ * tag); *n = their number.  More than cap: SGA_ERANGE, *n = the number needed, nothing removed, the lost counters
+ * neither returned nor cleared.  A drained second that receives further events gets new rows.  *lost_events /
+ * *lost_count (either may be NULL): tuples and their count sum that found no room in the table since the last
+ * successful drain -- returned and cleared.  Waits for the queued batches.  An engine without the log: SGA_EINVAL. */
+int sga_server_log_drain(sga_engine *e, int64_t before_ms, sga_server_log_row *rows, size_t cap, size_t *n,
+                         uint64_t *lost_events, int64_t *lost_count);
+
 /* ---- circuit breaker events (EventObserverRegistry; new entry points only) ---- */
 /* AbstractCircuitBreaker notifies every CircuitBreakerStateChangeObserver of each transition with (prevState,
  * newState, rule, snapshotValue) (CORE/slots/block/degrade/circuitbreaker/AbstractCircuitBreaker.java:102-164).

@@ -114,6 +114,11 @@ class SgaTreeRow(C.Structure):
                 ("view", SgaNodeView)]
 
 
+class SgaServerLogRow(C.Structure):  # sga_server_log_row: one aggregated key of the token server log
+    _fields_ = [("time_slot", C.c_int64), ("flow_id", C.c_int64), ("tag", C.c_uint64), ("count", C.c_int64),
+                ("events", C.c_uint32), ("kind", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 class SgaBlockRow(C.Structure):  # sga_block_row: one aggregated key of the block log
     _fields_ = [("time_slot", C.c_int64), ("tag", C.c_uint64), ("count", C.c_int64), ("resource", C.c_uint32),
                 ("origin", C.c_uint32), ("detail", C.c_uint32), ("events", C.c_uint32), ("decision", C.c_uint8),
@@ -279,6 +284,9 @@ SIGNATURES = {
     "sga_block_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_block_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "sga_server_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "sga_server_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "sga_block_rule_index": (C.c_int, [C.c_void_p, C.c_int8, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_cb_events_enable": (C.c_int, [C.c_void_p, C.c_uint32]),

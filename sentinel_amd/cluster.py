@@ -80,6 +80,9 @@ class Engine:
         self.set_hot_rules(hot_rules, hot_min_requests)
         self.set_small_batch(small_batch)
         self.clients: dict = {}  # client address -> dense id (concurrency tokens)
+        self.server_log_cap = 0  # 0: the token server log is off
+        # value key -> text of the parameter values request_param_tokens hashed (server_log's param|block lines)
+        self.param_texts: dict = {}
 
     def client_id(self, address: Optional[str]) -> int:
         """Dense id of a client address; null or "" -> SGA_CLIENT_NONE (a BAD_REQUEST)."""
@@ -110,6 +113,32 @@ class Engine:
         keys = ("hot_mode", "flags", "n_sort", "n_cold", "n_prio", "n_hot_next", "bd_lo", "bd_hi", "hot_err",
                 "n_pre", "lane_order_ok")
         return dict(zip(keys, [int(x) for x in v]))
+
+    # ---- token server log (ClusterServerStatLogUtil)
+    def server_log_enable(self, max_rows: int = 0) -> None:
+        """sga_server_log_enable: turns the engine's token server log on (0: its default of 65,536 rows), or
+        resizes it while it is empty.  server_log.ServerLogWriter writes sentinel-server.log from it."""
+        check(_lib.load().sga_server_log_enable(self._h, int(max_rows)), self._h, "serverLogEnable")
+        self.server_log_cap = max(64, 1 << (int(max_rows) - 1).bit_length()) if max_rows else 1 << 16
+
+    def server_log_rows(self, before_ms: Optional[int] = None):
+        """sga_server_log_drain: (rows, lost_events, lost_count).  rows: a server_log.SERVER_LOG_ROW_DTYPE array of
+        the aggregated tuples whose second is finished at before_ms (None: every row), sorted by (time_slot,
+        flow_id, kind, tag); the lost counters: tuples, and their count sum, that found no room in the table since
+        the last drain."""
+        from .server_log import SERVER_LOG_ROW_DTYPE
+        before = (1 << 63) - 1 if before_ms is None else int(before_ms)
+        cap = max(1, min(self.server_log_cap, 1024))
+        for _ in range(2):  # once more with the size SGA_ERANGE names
+            n, le, lc = C.c_size_t(), C.c_uint64(), C.c_int64()
+            out = np.zeros(cap, dtype=SERVER_LOG_ROW_DTYPE)
+            rc = _lib.load().sga_server_log_drain(self._h, before, out.ctypes.data, cap, C.byref(n), C.byref(le),
+                                                  C.byref(lc))
+            if rc != -34:  # SGA_ERANGE
+                break
+            cap = int(n.value)
+        check(rc, self._h, "serverLogDrain")
+        return out[:n.value].copy(), int(le.value), int(lc.value)
 
     @property
     def handle(self):
@@ -316,6 +345,8 @@ class GlobalRequestLimiter:
         return self.limits.get(namespace, 0.0)
 
 
+PARAM_TEXTS_MAX = 1 << 16  # Engine.param_texts entries at most
+
 TOKEN_DTYPE = np.dtype([("remaining", "<i4"), ("wait_in_ms", "<i2"), ("status", "i1"), ("reserved", "i1")])
 CONC_RESULT_DTYPE = np.dtype([("token_id", "<i8"), ("status", "<i4"), ("reserved", "<i4")])  # sga_concurrent_result
 
@@ -375,8 +406,14 @@ class DefaultTokenService:
         n = len(fid)
         off = np.zeros(n + 1, dtype=np.uint32)
         flat = []
+        texts = self.engine.param_texts if self.engine.server_log_cap else None
         for i, p in enumerate(params):
             vals = [param_value_key(v) for v in (p if p is not None else [])]
+            if texts is not None:  # bounded: a full map keeps what it has
+                from .block_log import java_text
+                for k, v in zip(vals, p if p is not None else []):
+                    if len(texts) < PARAM_TEXTS_MAX or k in texts:
+                        texts[k] = java_text(v)
             flat += vals
             off[i + 1] = off[i] + len(vals)
         vals = np.ascontiguousarray(flat if flat else [0], dtype=np.int64)

@@ -3527,7 +3527,8 @@ __global__ __launch_bounds__(kThreads) void k_pslow(CParamState st, BatchScratch
                                                     const uint32_t *__restrict__ voff,
                                                     const int64_t *__restrict__ values,
                                                     const uint32_t *__restrict__ vkey, int64_t ts_base,
-                                                    const uint32_t *__restrict__ ts_off, uint64_t *__restrict__ out) {
+                                                    const uint32_t *__restrict__ ts_off, uint64_t *__restrict__ out,
+                                                    uint32_t *__restrict__ bpos) {
     const uint32_t nflows = sc.counters[2];
     const uint32_t nruns = sc.counters[1];
     const uint32_t nvalid = sc.counters[0];
@@ -3554,6 +3555,7 @@ __global__ __launch_bounds__(kThreads) void k_pslow(CParamState st, BatchScratch
                 remaining = next;
                 if (next < 0) {
                     passed = false;
+                    if (bpos) bpos[i] = v - v0;  // blockObject's place in the collection (server log)
                     break;
                 }
             }
@@ -4483,7 +4485,7 @@ void cparam_lru_switch(const CParamState &st, const uint64_t *d_qoff, uint32_t n
 
 void cparam_stage2(const CParamState &st, BatchScratch &sc, CParamScratch &ps, const int32_t *acquire,
                    const uint32_t *voff, const int64_t *values, int64_t ts_base, const uint32_t *ts_off, uint32_t n,
-                   uint32_t nslow, void *out_v, hipStream_t s) {
+                   uint32_t nslow, void *out_v, hipStream_t s, uint32_t *bpos) {
     sc.counters_clean = 0;  // the stages use the control words
     if (n == 0) return;
     uint64_t *out = (uint64_t *)out_v;
@@ -4515,7 +4517,7 @@ void cparam_stage2(const CParamState &st, BatchScratch &sc, CParamScratch &ps, c
         const uint64_t *els = ps.els[np & 1];
         runs(els, st.nslots);
         hipLaunchKernelGGL(k_pslow, dim3(fb), dim3(kThreads), 0, s, st, sc, els, acquire, voff, values, ps.vkey,
-                           ts_base, ts_off, out);
+                           ts_base, ts_off, out, bpos);
     }
 }
 

@@ -373,14 +373,16 @@ void cparam_scratch_carve(CParamScratch &ps, void *base, size_t cap);
 
 // Batched DefaultTokenService.requestParamToken over DEVICE buffers (host API drives it and reads
 // st.ctl between the stages).  Stage 1: validation, rule lookup, namespace limiter, value/key
-// insertion, path choice.  Stage 2: key-parallel closed form + sequential per-rule replay.
+// insertion, path choice.  Stage 2: key-parallel closed form + sequential per-rule replay.  bpos (optional, the
+// server log's): per request the sequential path blocks, the position of the blocking value in its value list
+// (the closed form decides single-value requests only and writes nothing: position 0).
 void cparam_stage1(const CParamState &st, BatchScratch &sc, CParamScratch &ps, const int64_t *flow_id,
                    const int32_t *acquire, const uint32_t *voff, const int64_t *values, int64_t ts_base,
                    const uint32_t *ts_off, uint32_t n, void *out, hipStream_t stream, const LimiterPass *lims,
                    int nlims);
 void cparam_stage2(const CParamState &st, BatchScratch &sc, CParamScratch &ps, const int32_t *acquire,
                    const uint32_t *voff, const int64_t *values, int64_t ts_base, const uint32_t *ts_off, uint32_t n,
-                   uint32_t nslow, void *out, hipStream_t stream);
+                   uint32_t nslow, void *out, hipStream_t stream, uint32_t *bpos = nullptr);
 // ClusterParamMetric.getSum(value) at now (rotation side effect included); *d_out = -1 if no key
 void cparam_sum(const CParamState &st, uint32_t slot, int64_t value, int64_t now, int64_t *d_out, hipStream_t s);
 void cparam_init_rule(const CParamState &st, uint32_t slot, hipStream_t s);

@@ -223,9 +223,11 @@ __device__ __forceinline__ void pm_key_add(const CParamState &st, const PRulePar
 // request of the rule (the local path's sequential lanes): validation, rule lookup, then for each value
 // rem = threshold(value) - sum(value) / intervalInSec - acquire; any rem < 0 -> BLOCKED with no adds;
 // all pass -> every value added, OK with remaining (int) rem of the last value (-1 for several).
-// The namespace limiter is not applied (the host refuses namespaces that have one).
+// The namespace limiter is not applied (the host refuses namespaces that have one).  bpos (optional): on BLOCKED,
+// the position of the blocking value (blockObject) in the value list.
 __device__ inline uint64_t cparam_request_exact(const CParamState &st, int64_t flow_id, int32_t a,
-                                                const uint64_t *values, uint32_t nv, int64_t t, uint32_t req) {
+                                                const uint64_t *values, uint32_t nv, int64_t t, uint32_t req,
+                                                uint32_t *bpos = nullptr) {
     if (flow_id <= 0 || a <= 0 || nv == 0) return pack_result(TRS_BAD_REQUEST, 0, 0);
     if (!st.ctl) return pack_result(TRS_NO_RULE_EXISTS, 0, 0);
     const uint32_t slot = prule_lookup(st, flow_id);
@@ -243,6 +245,7 @@ __device__ inline uint64_t cparam_request_exact(const CParamState &st, int64_t f
         remaining = next;
         if (next < 0) {
             passed = false;
+            if (bpos) *bpos = v;
             break;
         }
     }

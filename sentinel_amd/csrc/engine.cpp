@@ -7,6 +7,7 @@
 #include "flow.hpp"
 #include "gateway.hpp"
 #include "gateway_api.hpp"
+#include "server_log.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -292,6 +293,26 @@ struct Engine {
     DevBuf<uint8_t> d_stage;
     DevBuf<int64_t> d_tmp7;
     DevBuf<NsLimiterDev> d_lim;  // one per namespace index (used when the namespace has a limiter)
+
+    // ---- token server log (sga_server_log_enable): off until enabled.  slog_tokens is the last step of a batch of
+    // the four-array form on its stream; a look-back sort that gave up fails the batch, whose requests add nothing.
+    ServerLog slog;
+    DevBuf<uint32_t> d_pbpos;  // parameter entry, log on: position of the blocking value per request
+    void slog_tokens(const int64_t *f, const int32_t *a, const uint8_t *p, const uint32_t *t, int64_t ts_base, size_t n,
+                     int simple, const void *out, hipStream_t s) {
+        if (!slog.on) return;
+        ReqIn in;
+        in.flow = f;
+        in.acq = a;
+        in.prio = simple ? nullptr : p;
+        in.ts = t;
+        SlogBatch b;
+        if (sga::radix64_lookback()) {
+            b.fail = scratch.radix.err;
+            b.fail_mask = 0xFFFFFFFFu;
+        }
+        slog.pass(in, ts_base, (uint32_t)n, simple ? kSlogSimple : kSlogDefault, out, b, s);
+    }
 
     // ---- cluster parameter flow
     std::vector<PSlotHost> pslots;
@@ -1193,6 +1214,7 @@ int sga_request_tokens_device(sga_engine *e, const int64_t *d_flow_id, const int
                                   0, d_out, s, lims.data(), (int)lims.size());
         g.last_sc = &g.scratch;
         SGA_HIP_CHECK(hipGetLastError());
+        g.slog_tokens(d_flow_id, d_acquire, d_prio, d_ts_off, ts_base, n, 0, d_out, s);
         g.leave_stream(s);
         return SGA_OK;
     });
@@ -1212,6 +1234,16 @@ int sga_request_tokens_packed_device(sga_engine *e, const sga_token_request *d_r
                                          (uint32_t)n, d_out, s, lims.data(), (int)lims.size());
         g.last_sc = &g.scratch;
         SGA_HIP_CHECK(hipGetLastError());
+        if (g.slog.on) {
+            sga::ReqIn in;
+            in.pk = reinterpret_cast<const uint32_t *>(d_req);
+            sga::SlogBatch b;
+            if (sga::radix64_lookback()) {
+                b.fail = g.scratch.radix.err;
+                b.fail_mask = 0xFFFFFFFFu;
+            }
+            g.slog.pass(in, ts_base, (uint32_t)n, sga::kSlogDefault, d_out, b, s);
+        }
         g.leave_stream(s);
         return SGA_OK;
     });
@@ -1239,6 +1271,7 @@ int sga_request_tokens_device_pipelined(sga_engine *e, const int64_t *d_flow_id,
                                           (uint32_t)n, 0, d_out, s, lims.data(), (int)lims.size());
                 g.last_sc = &g.scratch;
                 SGA_HIP_CHECK(hipGetLastError());
+                g.slog_tokens(d_flow_id, d_acquire, d_prio, d_ts_off, ts_base, n, 0, d_out, s);
                 g.leave_stream(s);
                 return SGA_OK;
             }
@@ -1267,6 +1300,8 @@ int sga_request_tokens_device_pipelined(sga_engine *e, const int64_t *d_flow_id,
             sga::cluster_decide_hot(st, sc, d_acquire, d_prio, ts_base, d_ts_off, (uint32_t)n, d_out, g.stream);
             SGA_HIP_CHECK(hipEventRecord(g.ev_dec[p], g.stream));
             g.dec_recorded[p] = true;
+            // the log reads the batch's inputs and results only: the next batch's stage 1 does not wait for it
+            g.slog_tokens(d_flow_id, d_acquire, d_prio, d_ts_off, ts_base, n, 0, d_out, g.stream);
             g.pipe_live = true;
             g.parity ^= 1;
             g.last_sc = &sc;
@@ -1371,6 +1406,7 @@ static int run_host_batch_pipelined(Engine &g, const int64_t *flow_id, const int
     sga::cluster_decide_batch(g.state(), g.scratch, g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, t0 + lo, g.d_in_ts.p,
                               (uint32_t)n, simple, g.d_out.p, g.stream, lims.data(), (int)lims.size());
     SGA_HIP_CHECK(hipGetLastError());
+    g.slog_tokens(g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, g.d_in_ts.p, t0 + lo, n, simple, g.d_out.p, g.stream);
     auto d2h = [&](size_t c) {
         const size_t s = c % K, c0 = c * C, m = std::min(C, n - c0);
         SGA_HIP_CHECK(hipMemcpyAsync(g.h_pin_out.p + s * C * 8, g.d_out.p + c0, m * 8, hipMemcpyDeviceToHost,
@@ -1430,6 +1466,7 @@ static int run_host_batch_registered(Engine &g, const int64_t *flow_id, const in
     sga::cluster_decide_batch(g.state(), g.scratch, g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, mm[0], g.d_in_ts.p,
                               (uint32_t)n, simple, g.d_out.p, g.stream, lims.data(), (int)lims.size());
     SGA_HIP_CHECK(hipGetLastError());
+    g.slog_tokens(g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, g.d_in_ts.p, mm[0], n, simple, g.d_out.p, g.stream);
     SGA_HIP_CHECK(hipMemcpyAsync(out, g.d_out.p, n * 8, hipMemcpyDeviceToHost, g.stream));
     SGA_HIP_CHECK(hipStreamSynchronize(g.stream));
     if (sga::radix64_lookback()) {
@@ -1484,6 +1521,8 @@ static int run_host_batch(Engine &g, const int64_t *flow_id, const int32_t *acqu
                                       reinterpret_cast<const uint32_t *>(d + 12 * n), (uint32_t)n, simple, g.d_out.p,
                                       g.stream, lims.data(), (int)lims.size());
             SGA_HIP_CHECK(hipGetLastError());
+            g.slog_tokens(reinterpret_cast<const int64_t *>(d), reinterpret_cast<const int32_t *>(d + 8 * n), d + 16 * n,
+                          reinterpret_cast<const uint32_t *>(d + 12 * n), lo, n, simple, g.d_out.p, g.stream);
             SGA_HIP_CHECK(hipMemcpyAsync(g.h_res.p, g.d_out.p, n * 8, hipMemcpyDeviceToHost, g.stream));
             SGA_HIP_CHECK(hipStreamSynchronize(g.stream));
             std::memcpy(out, g.h_res.p, n * 8);
@@ -1530,6 +1569,8 @@ static int run_host_batch(Engine &g, const int64_t *flow_id, const int32_t *acqu
         sga::cluster_decide_batch(g.state(), g.scratch, g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, lo, g.d_in_ts.p,
                                   (uint32_t)m, simple, g.d_out.p, g.stream, lims.data(), (int)lims.size());
         SGA_HIP_CHECK(hipGetLastError());
+        // before the next chunk reuses the staging buffers: same stream, in order
+        g.slog_tokens(g.d_in_fid.p, g.d_in_acq.p, g.d_in_prio.p, g.d_in_ts.p, lo, m, simple, g.d_out.p, g.stream);
         SGA_HIP_CHECK(hipMemcpyAsync(out + b, g.d_out.p, m * 8, hipMemcpyDeviceToHost, g.stream));
         SGA_HIP_CHECK(hipStreamSynchronize(g.stream));
         if (sga::radix64_lookback()) {  // a look-back that gave up would have sorted wrongly
@@ -2053,9 +2094,28 @@ int sga_request_param_tokens(sga_engine *e, const int64_t *flow_id, const int32_
                 g.cparam_lru_switch_host(ctl[4], g.stream);
                 st = g.pstate();  // the queue pool may have moved
             }
+            uint32_t *bpos = nullptr;  // the sequential path's side output, the log's only
+            if (g.slog.on) {
+                if (g.d_pbpos.n < cap) g.d_pbpos.alloc(cap);
+                bpos = g.d_pbpos.p;
+                SGA_HIP_CHECK(hipMemsetAsync(bpos, 0, m * 4, g.stream));  // the closed form decides single values: 0
+            }
             sga::cparam_stage2(st, g.scratch, g.pscratch, g.d_in_acq.p, g.d_in_voff.p, g.d_in_vals.p, lo, g.d_in_ts.p,
-                               (uint32_t)m, ctl[2], g.d_out.p, g.stream);
+                               (uint32_t)m, ctl[2], g.d_out.p, g.stream, bpos);
             SGA_HIP_CHECK(hipGetLastError());
+            if (g.slog.on) {
+                sga::ReqIn in;
+                in.flow = g.d_in_fid.p;
+                in.acq = g.d_in_acq.p;
+                in.ts = g.d_in_ts.p;
+                sga::SlogBatch sb;
+                sb.voff = g.d_in_voff.p;
+                sb.values = g.d_in_vals.p;
+                sb.bpos = bpos;
+                sb.fail = g.d_pctl.p + 1;
+                sb.fail_mask = 4u;  // the LRU queue check: the call fails
+                g.slog.pass(in, lo, (uint32_t)m, sga::kSlogParam, g.d_out.p, sb, g.stream);
+            }
             SGA_HIP_CHECK(hipMemcpyAsync(out + b, g.d_out.p, m * 8, hipMemcpyDeviceToHost, g.stream));
             uint32_t err = 0;
             SGA_HIP_CHECK(hipMemcpyAsync(&err, g.d_pctl.p + 1, 4, hipMemcpyDeviceToHost, g.stream));
@@ -2349,6 +2409,7 @@ int sga_rls_should_rate_limit_device(sga_engine *e, const uint32_t *d_desc_offse
         if (n_descriptors)
             sga::cluster_decide_batch(g.state(), g.scratch, g.d_in_fid.p, g.d_in_acq.p, nullptr, ts_base, g.d_in_ts.p,
                                       (uint32_t)n_descriptors, 1, g.d_out.p, s, lims.data(), (int)lims.size());
+        g.slog_tokens(g.d_in_fid.p, g.d_in_acq.p, nullptr, g.d_in_ts.p, ts_base, n_descriptors, 1, g.d_out.p, s);
         sga::rls_finish(d_desc_offsets, (uint32_t)n_requests, d_hits_addend, g.d_out.p, d_desc_status,
                         d_desc_remaining, d_code, s);
         SGA_HIP_CHECK(hipGetLastError());
@@ -2860,6 +2921,23 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
         return g.flow.block_log_drain(before_ms, rows, cap, n, lost_events, lost_count);
+    });
+}
+
+int sga_server_log_enable(sga_engine *e, uint32_t max_rows) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.slog.enable(max_rows, g.stream);
+    });
+}
+
+int sga_server_log_drain(sga_engine *e, int64_t before_ms, sga_server_log_row *rows, size_t cap, size_t *n,
+                         uint64_t *lost_events, int64_t *lost_count) {
+    static_assert(sizeof(sga_server_log_row) == 40, "server log row is 40 bytes");
+    if (e) (void)combine_round(e);  // requests waiting in the coalescing queue are decided (and logged) first
+    return guarded(e, [&](Engine &g) {  // guarded joins the pipeline: the engine stream then holds every queued batch
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.slog.drain(before_ms, rows, cap, n, lost_events, lost_count, g.stream);
     });
 }
 

@@ -279,8 +279,10 @@ class RlsBatcher:
     The mocked TimeUtil of the tests is `clock` (default wall-clock milliseconds)."""
 
     def __init__(self, rule_manager: EnvoyRlsRuleManager, window_us: int = 200, max_requests: int = 1 << 14,
-                 clock: Optional[Callable[[], int]] = None, decide=None):
+                 clock: Optional[Callable[[], int]] = None, decide=None, server_log=None):
         self.rm = rule_manager
+        self.server_log = server_log  # a server_log.ServerLogWriter: polled once a second of the clock by the batcher
+        self._log_second = None
         if decide is None:
             from .cluster import EnvoyRlsService
             svc = EnvoyRlsService(rule_manager.engine)
@@ -303,6 +305,8 @@ class RlsBatcher:
             self._stop = True
             self._cv.notify()
         self._t.join()
+        if self.server_log is not None:
+            self.server_log.poll(self.clock())
 
     def submit(self, domain: str, entries: List[List[Tuple[str, str]]], hits: int):
         c = _Call(domain, entries, hits)
@@ -354,6 +358,9 @@ class RlsBatcher:
             self.trace.append((o, f, h, now))
         code, st, rem = self.decide(o, f, h, np.full(len(batch), now, np.int64))
         self.batches += 1
+        if self.server_log is not None and now // 1000 != self._log_second:
+            self._log_second = now // 1000
+            self.server_log.poll(now)
         for r, c in enumerate(batch):
             stats = []
             for d in range(off[r], off[r + 1]):
@@ -384,9 +391,10 @@ class SentinelRlsGrpcServer:
 
     def __init__(self, rule_manager: EnvoyRlsRuleManager, port: int = DEFAULT_GRPC_PORT, host: str = "127.0.0.1",
                  window_us: int = 200, max_workers: int = 256, clock: Optional[Callable[[], int]] = None,
-                 decide=None):
+                 decide=None, server_log=None):
         import grpc
-        self.batcher = RlsBatcher(rule_manager, window_us=window_us, clock=clock, decide=decide)
+        self.batcher = RlsBatcher(rule_manager, window_us=window_us, clock=clock, decide=decide,
+                                  server_log=server_log)
         self._server = grpc.server(futures.ThreadPoolExecutor(max_workers=max_workers),
                                    options=[("grpc.so_reuseport", 0)])
         for ver in ("v2", "v3"):

@@ -130,8 +130,13 @@ class ConnectionManager:
 
 class ClusterTokenServer:
     def __init__(self, engine: Engine, host: str = "127.0.0.1", port: int = DEFAULT_CLUSTER_SERVER_PORT,
-                 window_us: int = 200, cap: int = 1 << 16, clock: Optional[Callable[[], int]] = None):
+                 window_us: int = 200, cap: int = 1 << 16, clock: Optional[Callable[[], int]] = None,
+                 server_log=None):
+        """server_log: a server_log.ServerLogWriter over this engine (after Engine.server_log_enable()); the batch
+        timer polls it once a second of the clock, stop() once more."""
         self.engine = engine
+        self.server_log = server_log
+        self._log_second = None
         self.svc = DefaultTokenService(engine)
         self.host, self.port = host, port
         self.window = window_us / 1e6
@@ -156,6 +161,8 @@ class ClusterTokenServer:
             self._server.close()
             await self._server.wait_closed()
         await self.flush()
+        if self.server_log is not None:
+            self.server_log.poll(self.clock())
 
     async def _on_conn(self, reader: asyncio.StreamReader, writer: asyncio.StreamWriter):
         cid = self._next_conn
@@ -259,6 +266,9 @@ class ClusterTokenServer:
                                                wait[idx], ping[idx])
             b.reset()
             self.conn_of = []
+            if self.server_log is not None and now // 1000 != self._log_second:  # once a second
+                self._log_second = now // 1000
+                self.server_log.poll(now)
         # one client that reset or closed its connection must not keep the others' responses back:
         # write errors drop that connection only
         for cid, data in frames.items():
