@@ -870,14 +870,27 @@ int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint
  *   SGA_SLOG_PARAM_BLOCK      requestParamToken BLOCKED; tag = the first value  count += 1,       events += 1
  *                             in collection order whose nextRemaining < 0
  * Nothing is formed for TOO_MANY_REQUEST, FAIL, NO_RULE_EXISTS and BAD_REQUEST (an empty value list among them)
- * nor for a batch that failed.  Off by default: an engine that never enables the log launches and allocates
- * nothing for it. */
+ * nor for a batch that failed.
+ * The concurrency checker writes to the same file (CS/flow/ConcurrentClusterFlowChecker.java:58,67,73,99), so every
+ * staged chunk of sga_concurrent_ops ends with a pass of its own behind the kernel that decided it.  One operation
+ * forms one tuple or none, in the second of the operation itself (a release counts in the second of the release):
+ *   SGA_SLOG_CONC_PASS        acquire answered OK                               count += acquire, events += 1
+ *   SGA_SLOG_CONC_BLOCK       acquire answered BLOCKED                          count += acquire, events += 1
+ *   SGA_SLOG_CONC_RELEASE     release answered RELEASE_OK; flow_id and the      count += the token's acquire,
+ *                             count are those of the token's node, not the call's                events += 1
+ * with tag 0.  BAD_REQUEST, NO_RULE_EXISTS and ALREADY_RELEASE (the second release of one token inside a batch among
+ * them) form nothing, and neither does an expiry pass (RegularExpireStrategy writes to RecordLog only).  This path
+ * has no failed batches: the pass is unconditional.
+ * Off by default: an engine that never enables the log launches and allocates nothing for it. */
 #define SGA_SLOG_FLOW_BLOCK 0
 #define SGA_SLOG_FLOW_BLOCK_PRIO 1
 #define SGA_SLOG_FLOW_WAITING 2
 #define SGA_SLOG_FLOW_PASS 3
 #define SGA_SLOG_PARAM_PASS 4
 #define SGA_SLOG_PARAM_BLOCK 5
+#define SGA_SLOG_CONC_PASS 6
+#define SGA_SLOG_CONC_BLOCK 7
+#define SGA_SLOG_CONC_RELEASE 8
 typedef struct sga_server_log_row {   /* sizeof == 40 */
     int64_t time_slot;   /* t - t % 1000 of the requests (StatLogger's rolling slot at intervalSeconds(1)) */
     int64_t flow_id;
@@ -900,6 +913,21 @@ int sga_server_log_enable(sga_engine *e, uint32_t max_rows);
  * successful drain -- returned and cleared.  Waits for the queued batches.  An engine without the log: SGA_EINVAL. */
 int sga_server_log_drain(sga_engine *e, int64_t before_ms, sga_server_log_row *rows, size_t cap, size_t *n,
                          uint64_t *lost_events, int64_t *lost_count);
+
+/* The gauges ClusterConcurrentCheckerLogListener writes once a second (CS/flow/statistic/concurrent/
+ * ClusterConcurrentCheckerLogListener.java:39-54): one row for every loaded cluster flow rule that is active, is in
+ * CurrentConcurrencyManager's map and has nowCalls != 0 (negative values are listed), sorted by flow_id; *n = their
+ * number.  *token_size (may be NULL): TokenCacheNodeManager.getSize().  The rows are compacted on the device, so the
+ * call copies back what it returns and nothing else.  More rows than cap: SGA_ERANGE, *n = the number needed, nothing
+ * written.  Waits for the engine stream, changes no state and does not need the log enabled.  An engine without
+ * concurrency state yet: *n = 0, *token_size = 0. */
+typedef struct sga_concurrent_gauge {   /* sizeof == 24 */
+    int64_t flow_id;
+    double  level;       /* ConcurrentClusterFlowChecker.calcGlobalThreshold(rule): count, or count * connectedCount */
+    int32_t now_calls;   /* CurrentConcurrencyManager value, != 0 */
+    int32_t reserved;    /* zero */
+} sga_concurrent_gauge;
+int sga_concurrent_gauges(sga_engine *e, sga_concurrent_gauge *rows, size_t cap, size_t *n, uint64_t *token_size);
 
 /* ---- circuit breaker events (EventObserverRegistry; new entry points only) ---- */
 /* AbstractCircuitBreaker notifies every CircuitBreakerStateChangeObserver of each transition with (prevState,

@@ -119,6 +119,10 @@ class SgaServerLogRow(C.Structure):  # sga_server_log_row: one aggregated key of
                 ("events", C.c_uint32), ("kind", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
+class SgaConcurrentGauge(C.Structure):  # sga_concurrent_gauge: one rule's line of the concurrency log listener
+    _fields_ = [("flow_id", C.c_int64), ("level", C.c_double), ("now_calls", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SgaBlockRow(C.Structure):  # sga_block_row: one aggregated key of the block log
     _fields_ = [("time_slot", C.c_int64), ("tag", C.c_uint64), ("count", C.c_int64), ("resource", C.c_uint32),
                 ("origin", C.c_uint32), ("detail", C.c_uint32), ("events", C.c_uint32), ("decision", C.c_uint8),
@@ -287,7 +291,9 @@ SIGNATURES = {
     "sga_server_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_server_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
-    "sga_block_rule_index": (C.c_int, [C.c_void_p, C.c_int8, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "sga_concurrent_gauges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_uint64)]),
+    "sga_block_rule_index":(C.c_int, [C.c_void_p, C.c_int8, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "sga_circuit_breaker_state": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "sga_cb_events_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_cb_events_drain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),

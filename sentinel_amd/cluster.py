@@ -83,6 +83,8 @@ class Engine:
         self.server_log_cap = 0  # 0: the token server log is off
         # value key -> text of the parameter values request_param_tokens hashed (server_log's param|block lines)
         self.param_texts: dict = {}
+        # flowId -> resource name of the rules ClusterFlowRuleManager.load_rules saw (server_log's gauge lines)
+        self.flow_resources: dict = {}
 
     def client_id(self, address: Optional[str]) -> int:
         """Dense id of a client address; null or "" -> SGA_CLIENT_NONE (a BAD_REQUEST)."""
@@ -140,6 +142,22 @@ class Engine:
         check(rc, self._h, "serverLogDrain")
         return out[:n.value].copy(), int(le.value), int(lc.value)
 
+    def concurrent_gauges(self):
+        """sga_concurrent_gauges: (rows, token_size).  rows: a CONC_GAUGE_DTYPE array, one row for every active rule
+        of the concurrency map whose nowCalls != 0 (flow_id, calcGlobalThreshold level, now_calls), sorted by
+        flow_id; token_size: TokenCacheNodeManager.getSize().  What ClusterConcurrentCheckerLogListener logs once
+        a second; reads state only and does not need the server log enabled."""
+        cap = 1024
+        for _ in range(2):  # once more with the size SGA_ERANGE names
+            n, size = C.c_size_t(), C.c_uint64()
+            out = np.zeros(cap, dtype=CONC_GAUGE_DTYPE)
+            rc = _lib.load().sga_concurrent_gauges(self._h, out.ctypes.data, cap, C.byref(n), C.byref(size))
+            if rc != -34:  # SGA_ERANGE
+                break
+            cap = int(n.value)
+        check(rc, self._h, "concurrentGauges")
+        return out[:n.value].copy(), int(size.value)
+
     @property
     def handle(self):
         return self._h
@@ -161,6 +179,9 @@ class Engine:
     def __exit__(self, *a):
         self.close()
 
+
+# one sga_concurrent_gauge (sga_concurrent_gauges)
+CONC_GAUGE_DTYPE = np.dtype([("flow_id", "<i8"), ("level", "<f8"), ("now_calls", "<i4"), ("reserved", "<i4")])
 
 # sga_cluster_flow_rule as a numpy record (bulk loads; the oracle's orc_cluster_rule has the same layout)
 CLUSTER_RULE_DTYPE = np.dtype([("flow_id", "<i8"), ("count", "<f8"), ("threshold_type", "<i4"), ("sample_count", "<i4"),
@@ -195,7 +216,14 @@ class ClusterFlowRuleManager:
         rules = [r for r in rules if r.cluster_mode]  # applyClusterFlowRule skips !isClusterMode
         arr = _rules_array(rules)
         rc = _lib.load().sga_load_cluster_flow_rules(self.engine.handle, namespace.encode(), arr, len(rules))
-        return check(rc, self.engine.handle, "loadRules")
+        rc = check(rc, self.engine.handle, "loadRules")
+        names = getattr(self.engine, "flow_resources", None)
+        if names is not None:  # the C rule carries no name: kept for the gauge lines, as param_texts is
+            for r in rules:
+                fid = r.cluster_config.flow_id
+                if fid is not None and r.resource is not None:
+                    names[int(fid)] = r.resource
+        return rc
 
     def load_rule_arrays(self, namespace: str, flow_id, count, threshold_type=1, sample_count=10,
                          window_interval_ms=1000) -> int:
@@ -453,7 +481,9 @@ class DefaultTokenService:
         return TokenResult(int(r["status"]), token_id=int(r["token_id"]))
 
     def release_concurrent_token(self, token_id: int, now: int = 0) -> int:
-        """ConcurrentClusterFlowChecker.releaseConcurrentToken status (the SPI method returns void)."""
+        """ConcurrentClusterFlowChecker.releaseConcurrentToken status (the SPI method returns void).  `now` decides
+        nothing, but with the server log on it is the second the concurrent|release line is written under: a caller
+        that leaves it at 0 gets that line in second 0."""
         return int(self.concurrent_ops([CONCURRENT_RELEASE], [CLIENT_NONE], [token_id], [0], [now])[0]["status"])
 
     def expire_concurrent_tokens(self, now: int, online_addresses=()) -> int:

@@ -225,6 +225,40 @@ __global__ void k_conc_find(ConcState st, int64_t token, TokenEntry *out) {
     }
 }
 
+// ClusterConcurrentCheckerLogListener's gauges: one lane a rule slot.  A slot is listed when its nowCalls != 0 and
+// its flowId still leads back to it through the lookup of active rules (a freed or cleared slot does not).  The
+// listed lanes of a wave are compacted by a ballot and a prefix count and take their places with one atomic on the
+// counter per wave (the per-wave append of flow.hip's lists); rows past `cap` are counted, not written.
+__global__ void __launch_bounds__(kThreads) k_conc_gauges(ConcState st, sga_concurrent_gauge *out, uint32_t cap,
+                                                          uint32_t *count) {
+    const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
+    int32_t calls = 0;
+    int64_t fid = 0;
+    bool listed = false;
+    if (s < st.cs.nslots) {
+        calls = st.now_calls[s];
+        if (calls != 0) {
+            fid = st.cs.slot_fid[s];
+            listed = rule_slot(st.cs, fid) == s;
+        }
+    }
+    const unsigned long long m = __ballot(listed);
+    if (!m) return;
+    const int lane = (int)(threadIdx.x & 63u), lead = __ffsll(m) - 1;
+    uint32_t base = 0;
+    if (lane == lead) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, lead, 64);
+    if (!listed) return;
+    const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (pos >= cap) return;
+    sga_concurrent_gauge g;
+    g.flow_id = fid;
+    g.level = st.cparam[s].thr;
+    g.now_calls = calls;
+    g.reserved = 0;
+    out[pos] = g;
+}
+
 size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t conc_hist_entries(size_t cap) {
@@ -294,6 +328,13 @@ void conc_rehash(const TokenEntry *old, uint32_t old_n, TokenEntry *nt, uint32_t
 void conc_reset_calls(int32_t *now_calls, const uint32_t *slots, uint32_t n, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_conc_reset, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, now_calls, slots, n);
+}
+
+void conc_gauges(const ConcState &st, sga_concurrent_gauge *out, uint32_t cap, uint32_t *count, hipStream_t s) {
+    SGA_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
+    const uint32_t n = st.cs.nslots;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_conc_gauges, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, st, out, cap, count);
 }
 
 void conc_find(const ConcState &st, int64_t token, TokenEntry *d_out, hipStream_t s) {

@@ -66,6 +66,9 @@ void conc_expire(const ConcState &st, int64_t now, const uint32_t *online_bits, 
 void conc_rehash(const TokenEntry *old, uint32_t old_n, TokenEntry *nt, uint32_t nmask, hipStream_t s);
 // CurrentConcurrencyManager.put(flowId, 0) for the listed slots.
 void conc_reset_calls(int32_t *now_calls, const uint32_t *slots, uint32_t n, hipStream_t s);
+// ClusterConcurrentCheckerLogListener's per-flow gauges: the active rules in the concurrency map whose nowCalls != 0,
+// compacted into out[0 .. min(*count, cap)) in no particular order; *count (device) = how many there are.
+void conc_gauges(const ConcState &st, sga_concurrent_gauge *out, uint32_t cap, uint32_t *count, hipStream_t s);
 // TokenCacheNodeManager.getTokenCacheNode: the live entry of `token` (state 0 when absent).
 void conc_find(const ConcState &st, int64_t token, TokenEntry *d_out, hipStream_t s);
 

@@ -363,6 +363,8 @@ struct Engine {
     DevBuf<int32_t> d_cin_acq;
     DevBuf<sga_concurrent_result> d_cout;
     DevBuf<TokenEntry> d_tfind;
+    DevBuf<sga_concurrent_gauge> d_gauge;  // sga_concurrent_gauges: the compacted rows, created with the first call
+    DevBuf<uint32_t> d_gauge_n;
 
     ConcState cstate() const {
         ConcState c{};
@@ -2247,6 +2249,11 @@ int sga_concurrent_ops(sga_engine *e, const uint8_t *op, const uint32_t *client,
             sga::conc_ops(g.cstate(), g.cscratch, g.d_cin_op.p, g.d_cin_client.p, g.d_cin_id.p, g.d_cin_acq.p,
                           g.d_cin_ts.p, (uint32_t)m, g.token_base, g.d_cout.p, g.stream);
             SGA_HIP_CHECK(hipGetLastError());
+            if (g.slog.on) {  // the checker's concurrent|... sums, before the staging buffers and the epoch move on
+                sga::SlogConc c{g.d_cin_op.p, g.d_cin_id.p, g.d_cin_acq.p, g.d_cin_ts.p, g.d_cout.p, g.cscratch.aux,
+                                g.d_tok.p, g.tmask};
+                g.slog.pass_conc(c, (uint32_t)m, g.stream);
+            }
             g.token_base += m;
             SGA_HIP_CHECK(hipMemcpyAsync(out + b, g.d_cout.p, m * sizeof(sga_concurrent_result), hipMemcpyDeviceToHost,
                                          g.stream));
@@ -2307,6 +2314,44 @@ int sga_concurrent_token_count(sga_engine *e, uint64_t *n) {
     if (!n) return SGA_EINVAL;
     return guarded(e, [&](Engine &g) {
         *n = g.tlive;
+        return SGA_OK;
+    });
+}
+
+// ClusterConcurrentCheckerLogListener.collectInformation, CS/flow/statistic/concurrent/
+// ClusterConcurrentCheckerLogListener.java:39-54
+int sga_concurrent_gauges(sga_engine *e, sga_concurrent_gauge *rows, size_t cap, size_t *n, uint64_t *token_size) {
+    if (!n || (cap && !rows)) return SGA_EINVAL;
+    static_assert(sizeof(sga_concurrent_gauge) == 24, "concurrency gauge is 24 bytes");
+    return guarded(e, [&](Engine &g) {
+        *n = 0;
+        if (token_size) *token_size = 0;
+        if (!g.d_cscratch.p || g.slots.empty()) return SGA_OK;  // no concurrency state yet
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        if (!g.d_gauge.p) {
+            g.d_gauge.alloc(1024);
+            g.d_gauge_n.alloc(1);
+        }
+        uint32_t c[2] = {0, 0};  // rows listed, live tokens
+        for (int pass = 0; pass < 2; ++pass) {  // once more when the device buffer was too small for the rows
+            sga::conc_gauges(g.cstate(), g.d_gauge.p, (uint32_t)g.d_gauge.n, g.d_gauge_n.p, g.stream);
+            SGA_HIP_CHECK(hipGetLastError());
+            SGA_HIP_CHECK(hipMemcpyAsync(&c[0], g.d_gauge_n.p, 4, hipMemcpyDeviceToHost, g.stream));
+            SGA_HIP_CHECK(hipMemcpyAsync(&c[1], g.d_tctr.p, 4, hipMemcpyDeviceToHost, g.stream));
+            SGA_HIP_CHECK(hipStreamSynchronize(g.stream));
+            if (c[0] <= g.d_gauge.n) break;
+            g.d_gauge.alloc(c[0]);
+        }
+        *n = c[0];
+        if (token_size) *token_size = c[1];
+        if (c[0] > cap) return SGA_ERANGE;
+        if (c[0]) {
+            SGA_HIP_CHECK(hipMemcpyAsync(rows, g.d_gauge.p, (size_t)c[0] * sizeof(sga_concurrent_gauge),
+                                         hipMemcpyDeviceToHost, g.stream));
+            SGA_HIP_CHECK(hipStreamSynchronize(g.stream));
+            std::sort(rows, rows + c[0],
+                      [](const sga_concurrent_gauge &x, const sga_concurrent_gauge &y) { return x.flow_id < y.flow_id; });
+        }
         return SGA_OK;
     });
 }

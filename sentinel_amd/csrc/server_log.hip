@@ -60,20 +60,15 @@ __device__ __forceinline__ void slog_update(const SlogTab &tb, const SlogKey &k,
     atomicAdd(&tb.ctl[1], (unsigned long long)sum);
 }
 
-// One lane a request, grid-stride over whole blocks (every lane of a wave stays in the loop: the combine below is
-// wave-wide).  The lane reads the request's 8-byte result and forms at most one tuple (the table in the header:
-// which one depends on the checker that decided the batch).  Then the wave combines before touching memory, as
-// k_blog_add does: while a lane holds an unmerged tuple, the first such lane's hash is broadcast and the lanes
-// holding the same one sum their counts and count themselves -- registers only.  After that loop the first lanes
-// of all the tuples update the table side by side.  A tuple that at least two lanes share can become the wave's
-// held tuple instead: its sums stay in registers over the wave's later tiles, which merge into it first, and reach
-// the table once, at the end or when a tuple with more lanes in a tile takes its place.  A batch of blocks on one
-// hot rule costs two atomics a wave, not two a lane.
-__global__ __launch_bounds__(kSlogThreads) void k_slog_add(SlogTab tb, ReqIn in, int64_t ts_base, uint32_t n,
-                                                           int checker, const uint64_t *__restrict__ res,
-                                                           SlogBatch b) {
-    if (b.fail && (*b.fail & b.fail_mask)) return;  // the batch failed: nothing is logged
-    const int lane = (int)(threadIdx.x & 63u);
+// The wave's combine, shared by k_slog_add and k_slog_conc: the kernels differ only in how a lane forms its tuple.
+// Every lane of the wave calls add() once a tile with (has, key, hash, add) and flush() once at the end.  While a
+// lane holds an unmerged tuple, the first such lane's hash is broadcast and the lanes holding the same one sum their
+// counts and count themselves -- registers only, as k_blog_add does.  After that loop the first lanes of all the
+// tuples update the table side by side.  A tuple that at least two lanes share can become the wave's held tuple
+// instead: its sums stay in registers over the wave's later tiles, which merge into it first, and reach the table
+// once, at the end or when a tuple with more lanes in a tile takes its place.  A batch of blocks on one hot rule
+// costs two atomics a wave, not two a lane.
+struct SlogWave {
     // the held tuple: hash, sums and owner lane are wave-uniform, the key fields stay in lane hl's hk
     bool held = false;
     uint64_t hh = 0;
@@ -81,45 +76,9 @@ __global__ __launch_bounds__(kSlogThreads) void k_slog_add(SlogTab tb, ReqIn in,
     uint32_t hcnt = 0;
     int hl = 0;
     SlogKey hk{};
-    for (uint32_t i0 = blockIdx.x * kSlogThreads; i0 < n; i0 += gridDim.x * kSlogThreads) {
-        const uint32_t i = i0 + threadIdx.x;
-        bool has = false;
-        SlogKey k{};
-        int64_t add = 1;
-        uint64_t h = 0;
-        if (i < n) {
-            const int st = slog_status(res[i]);
-            if (checker == kSlogParam) {
-                const uint32_t v0 = b.voff[i], nv = b.voff[i + 1] - v0;
-                if (nv && st == SGA_TOKEN_OK) {
-                    has = true;
-                    k.kind = SGA_SLOG_PARAM_PASS;
-                } else if (nv && st == SGA_TOKEN_BLOCKED) {
-                    has = true;
-                    k.kind = SGA_SLOG_PARAM_BLOCK;
-                    uint32_t pos = b.bpos ? b.bpos[i] : 0u;
-                    if (pos >= nv) pos = 0;
-                    k.tag = (uint64_t)b.values[v0 + pos];
-                }
-            } else if (st == SGA_TOKEN_BLOCKED) {
-                has = true;
-                k.kind = (checker == kSlogDefault && in.prio_at(i)) ? SGA_SLOG_FLOW_BLOCK_PRIO : SGA_SLOG_FLOW_BLOCK;
-                add = (int64_t)in.acq_at(i);
-            } else if (st == SGA_TOKEN_SHOULD_WAIT) {
-                has = true;
-                k.kind = SGA_SLOG_FLOW_WAITING;
-            } else if (st == SGA_TOKEN_OK && checker == kSlogSimple) {
-                has = true;
-                k.kind = SGA_SLOG_FLOW_PASS;
-                add = (int64_t)in.acq_at(i);
-            }
-            if (has) {
-                const int64_t t = ts_base + (int64_t)in.ts_at(i);
-                k.time_slot = t - t % 1000;
-                k.flow_id = in.flow_at(i);
-                h = slog_hash(k);
-            }
-        }
+
+    __device__ __forceinline__ void add(const SlogTab &tb, int lane, bool has, const SlogKey &k, uint64_t h,
+                                        int64_t add) {
         unsigned long long pend = __ballot(has);
         uint32_t hm = 0;  // lanes of this tile that merged into the held tuple
         if (held && pend) {
@@ -165,7 +124,106 @@ __global__ __launch_bounds__(kSlogThreads) void k_slog_add(SlogTab tb, ReqIn in,
         }
         if (first) slog_update(tb, k, h, gsum, gcnt);
     }
-    if (held && lane == hl) slog_update(tb, hk, hh, hsum, hcnt);
+
+    __device__ __forceinline__ void flush(const SlogTab &tb, int lane) {
+        if (held && lane == hl) slog_update(tb, hk, hh, hsum, hcnt);
+    }
+};
+
+// One lane a request, grid-stride over whole blocks (every lane of a wave stays in the loop: the combine is
+// wave-wide).  The lane reads the request's 8-byte result and forms at most one tuple (the table in the header:
+// which one depends on the checker that decided the batch); SlogWave does the rest.
+__global__ __launch_bounds__(kSlogThreads) void k_slog_add(SlogTab tb, ReqIn in, int64_t ts_base, uint32_t n,
+                                                           int checker, const uint64_t *__restrict__ res,
+                                                           SlogBatch b) {
+    if (b.fail && (*b.fail & b.fail_mask)) return;  // the batch failed: nothing is logged
+    const int lane = (int)(threadIdx.x & 63u);
+    SlogWave w;
+    for (uint32_t i0 = blockIdx.x * kSlogThreads; i0 < n; i0 += gridDim.x * kSlogThreads) {
+        const uint32_t i = i0 + threadIdx.x;
+        bool has = false;
+        SlogKey k{};
+        int64_t add = 1;
+        uint64_t h = 0;
+        if (i < n) {
+            const int st = slog_status(res[i]);
+            if (checker == kSlogParam) {
+                const uint32_t v0 = b.voff[i], nv = b.voff[i + 1] - v0;
+                if (nv && st == SGA_TOKEN_OK) {
+                    has = true;
+                    k.kind = SGA_SLOG_PARAM_PASS;
+                } else if (nv && st == SGA_TOKEN_BLOCKED) {
+                    has = true;
+                    k.kind = SGA_SLOG_PARAM_BLOCK;
+                    uint32_t pos = b.bpos ? b.bpos[i] : 0u;
+                    if (pos >= nv) pos = 0;
+                    k.tag = (uint64_t)b.values[v0 + pos];
+                }
+            } else if (st == SGA_TOKEN_BLOCKED) {
+                has = true;
+                k.kind = (checker == kSlogDefault && in.prio_at(i)) ? SGA_SLOG_FLOW_BLOCK_PRIO : SGA_SLOG_FLOW_BLOCK;
+                add = (int64_t)in.acq_at(i);
+            } else if (st == SGA_TOKEN_SHOULD_WAIT) {
+                has = true;
+                k.kind = SGA_SLOG_FLOW_WAITING;
+            } else if (st == SGA_TOKEN_OK && checker == kSlogSimple) {
+                has = true;
+                k.kind = SGA_SLOG_FLOW_PASS;
+                add = (int64_t)in.acq_at(i);
+            }
+            if (has) {
+                const int64_t t = ts_base + (int64_t)in.ts_at(i);
+                k.time_slot = t - t % 1000;
+                k.flow_id = in.flow_at(i);
+                h = slog_hash(k);
+            }
+        }
+        w.add(tb, lane, has, k, h, add);
+    }
+    w.flush(tb, lane);
+}
+
+// The concurrency checker's lines (ConcurrentClusterFlowChecker.java:58,67,73,99), behind k_conc_runs of one staged
+// chunk: one lane an operation.  The lane reads the operation and its 16-byte result's status; an acquire answered
+// OK or BLOCKED forms (second of ts, id, CONC_PASS / CONC_BLOCK) with its acquireCount, a release answered
+// RELEASE_OK forms CONC_RELEASE under the flowId and acquireCount of its token's node: tok[aux[i]], a tombstone of
+// the current epoch that nothing overwrites until a later batch.  Every other status forms nothing.
+__global__ __launch_bounds__(kSlogThreads) void k_slog_conc(SlogTab tb, SlogConc c, uint32_t n) {
+    const int lane = (int)(threadIdx.x & 63u);
+    SlogWave w;
+    for (uint32_t i0 = blockIdx.x * kSlogThreads; i0 < n; i0 += gridDim.x * kSlogThreads) {
+        const uint32_t i = i0 + threadIdx.x;
+        bool has = false;
+        SlogKey k{};
+        int64_t add = 0;
+        uint64_t h = 0;
+        if (i < n) {
+            const int st = c.res[i].status;
+            if (c.op[i] == SGA_CONCURRENT_ACQUIRE) {
+                if (st == SGA_TOKEN_OK || st == SGA_TOKEN_BLOCKED) {
+                    has = true;
+                    k.kind = st == SGA_TOKEN_OK ? SGA_SLOG_CONC_PASS : SGA_SLOG_CONC_BLOCK;
+                    k.flow_id = c.id[i];
+                    add = (int64_t)c.acquire[i];
+                }
+            } else if (st == SGA_TOKEN_RELEASE_OK) {
+                const uint32_t ix = c.aux[i];
+                if (ix <= c.tmask) {
+                    has = true;
+                    k.kind = SGA_SLOG_CONC_RELEASE;
+                    k.flow_id = c.tok[ix].flow_id;
+                    add = (int64_t)c.tok[ix].acquire;
+                }
+            }
+            if (has) {
+                const int64_t t = c.ts[i];
+                k.time_slot = t - t % 1000;
+                h = slog_hash(k);
+            }
+        }
+        w.add(tb, lane, has, k, h, add);
+    }
+    w.flush(tb, lane);
 }
 
 // Drain, first half: the rows of finished seconds (time_slot <= limit) copied out, counted, nothing removed yet
@@ -232,13 +290,24 @@ int ServerLog::enable(uint32_t max_rows, hipStream_t stream) {
     return SGA_OK;
 }
 
+// blocks of a pass over n requests: kSlogTiles tiles a block at least
+static uint32_t slog_blocks(uint32_t n) {
+    const uint32_t per = kSlogTiles * kSlogThreads;
+    return std::min<uint32_t>((n + per - 1) / per, 512);
+}
+
 void ServerLog::pass(const ReqIn &in, int64_t ts_base, uint32_t n, int checker, const void *results,
                      const SlogBatch &b, hipStream_t s) {
     if (!on || n == 0) return;
-    const uint32_t per = kSlogTiles * kSlogThreads;
-    const uint32_t nb = std::min<uint32_t>((n + per - 1) / per, 512);
+    const uint32_t nb = slog_blocks(n);
     hipLaunchKernelGGL(k_slog_add, dim3(nb), dim3(kSlogThreads), 0, s, tab(live), in, ts_base, n, checker,
                        (const uint64_t *)results, b);
+    SGA_HIP_CHECK(hipGetLastError());
+}
+
+void ServerLog::pass_conc(const SlogConc &c, uint32_t n, hipStream_t s) {
+    if (!on || n == 0) return;
+    hipLaunchKernelGGL(k_slog_conc, dim3(slog_blocks(n)), dim3(kSlogThreads), 0, s, tab(live), c, n);
     SGA_HIP_CHECK(hipGetLastError());
 }
 

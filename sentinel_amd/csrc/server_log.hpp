@@ -4,6 +4,7 @@
 #include "../../include/sentinel_amd.h"
 #include "cluster.hpp"
 #include "common.hpp"
+#include "concurrent.hpp"
 
 namespace sga {
 
@@ -34,6 +35,20 @@ struct SlogBatch {
     uint32_t fail_mask = 0;
 };
 
+// What a concurrency chunk hands to its pass (k_slog_conc): the staged operations, their results, and where a
+// release finds its token's node -- aux[i] is the entry k_conc_classify found, a tombstone of the current epoch once
+// k_conc_runs answered RELEASE_OK.
+struct SlogConc {
+    const uint8_t *op;
+    const int64_t *id;
+    const int32_t *acquire;
+    const int64_t *ts;
+    const sga_concurrent_result *res;
+    const uint32_t *aux;
+    const TokenEntry *tok;
+    uint32_t tmask;
+};
+
 struct ServerLog {
     bool on = false;
     uint32_t slots = 0;
@@ -48,6 +63,8 @@ struct ServerLog {
     // The last kernel of a token batch, on the batch's stream.  Nothing when the log is off.
     void pass(const ReqIn &in, int64_t ts_base, uint32_t n, int checker, const void *results, const SlogBatch &b,
               hipStream_t s);
+    // The last kernel of a concurrency chunk, behind k_conc_runs on the engine stream.  Nothing when the log is off.
+    void pass_conc(const SlogConc &c, uint32_t n, hipStream_t s);
     int drain(int64_t before_ms, sga_server_log_row *rows, size_t cap, size_t *n, uint64_t *lost_events,
               int64_t *lost_count, hipStream_t stream);
 };
