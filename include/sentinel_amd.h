@@ -855,6 +855,67 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
  * resource's rules: SGA_EINVAL. */
 int sga_block_rule_index(sga_engine *e, int8_t decision, uint32_t resource, uint32_t detail, uint32_t *index);
 
+/* ---- metric extensions (StatisticSlotCallbackRegistry; new entry points only) ---- */
+/* MetricCallbackInit registers MetricEntryCallback and MetricExitCallback with StatisticSlotCallbackRegistry;
+ * StatisticSlot (CORE/slots/statistic/StatisticSlot.java:65-175) calls them on every pass, block and exit, and they
+ * fan out to every MetricExtension (CORE/metric/extension/): cumulative counters per resource, as opposed to the
+ * nodes' sliding windows.  The engine keeps what those calls would have summed: once enabled, every chunk of every
+ * submit entry (host and device, the sga_event_* queue included) ends with one pass that adds the chunk's events to
+ * engine-resident 64-bit sums, exact and kept until drained.  By the caller's kind and the final decision:
+ *   SGA_KIND_ENTRY, SGA_PASS or SGA_PASS_WAIT     pass += acquire, pass_events += 1 (onPass runs in the
+ *                                                 PriorityWaitException branch too, where the node's second
+ *                                                 window gets the pass only in the second it was borrowed from)
+ *   SGA_KIND_ENTRY, SGA_BLOCK_*                   a block row (resource, origin, decision, wait_ms as detail)
+ *   SGA_KIND_EXIT                                 success += acquire, exits += 1, rt_sum += rt, rt_max = max(rt) --
+ *                                                 rt as given, neither capped at statistic_max_rt nor made positive;
+ *                                                 with SGA_EV_ERROR also exception += acquire, exception_events += 1
+ *   SGA_KIND_BLOCKED                              a block row (resource, origin, 0, 0): the exception was thrown
+ *                                                 outside the engine
+ *   SGA_KIND_REVOKE                               the same block row, and the entry's pass taken back:
+ *                                                 pass -= acquire, pass_events -= 1
+ * A revoke drained apart from its entry shows as a negative pass: the sums are signed deltas.  Counted for nothing: a
+ * resource id >= n_resources, and every event of a chunk the device entry refused (-1).  The parameter of a
+ * SGA_BLOCK_PARAM is not part of a block row's key.  Off by default: an engine that never enables the sums launches
+ * and allocates nothing for them. */
+typedef struct sga_metric_res_row {   /* sizeof == 72 */
+    int64_t pass;              /* MetricExtension.addPass: sum of acquire */
+    int64_t pass_events;       /* onPass calls = increaseThreadNum calls */
+    int64_t success;           /* addSuccess: sum of acquire over exits */
+    int64_t exits;             /* onExit calls = decreaseThreadNum calls */
+    int64_t exception;         /* addException: sum of acquire over exits with SGA_EV_ERROR */
+    int64_t exception_events;
+    int64_t rt_sum;            /* addRt: sum of rt over exits */
+    int64_t rt_max;            /* the largest rt of an exit, at least 0 (0 without exits) */
+    uint32_t resource;
+    uint32_t reserved;
+} sga_metric_res_row;
+
+typedef struct sga_metric_block_row {   /* sizeof == 32 */
+    int64_t block;             /* addBlock: sum of acquire */
+    int64_t block_events;      /* onBlocked calls */
+    uint32_t resource;
+    uint32_t origin;           /* 0 when the call had no origin array */
+    uint32_t detail;           /* the block detail wait_ms carried (sga_block_rule_index names the rule) */
+    uint8_t decision;          /* SGA_BLOCK_*; 0: a kind 2 / 3 event (a plain BlockException) */
+    uint8_t reserved[3];
+} sga_metric_block_row;
+
+/* Turns the sums on (after sga_flow_set_resources) with room for max_block_rows block rows (0: the default of
+ * 65,536; at least 64; rounded up to a power of two); the per-resource sums are one 64-byte line per resource and
+ * cannot overflow.  Two block keys whose 64-bit hashes collide share a row.  Events submitted before the call are not
+ * counted.  Calling it again resizes the block table while nothing is pending; with sums pending: SGA_EINVAL. */
+int sga_metric_ext_enable(sga_engine *e, uint32_t max_block_rows);
+
+/* Moves out everything summed since the last drain: the resources with any non-zero sum, sorted by resource, and all
+ * block rows, sorted by (resource, origin, decision, detail); *n_res / *n_block = their numbers.  If either cap is too
+ * small: SGA_ERANGE, both numbers as needed, nothing removed, the lost counters neither returned nor cleared.
+ * *lost_events / *lost_count (either may be NULL): blocked entries and their acquire sum that found no room in the
+ * block table since the last successful drain -- returned and cleared.  Waits for the event queue and the engine
+ * stream.  An engine without the sums: SGA_EINVAL. */
+int sga_metric_ext_drain(sga_engine *e, sga_metric_res_row *res_rows, size_t res_cap, size_t *n_res,
+                         sga_metric_block_row *block_rows, size_t block_cap, size_t *n_block, uint64_t *lost_events,
+                         int64_t *lost_count);
+
 /* ---- token server log (ClusterServerStatLogUtil; new entry points only) ---- */
 /* The cluster checkers record what they refused through ClusterServerStatLogUtil.log(msg[, count])
  * (CS/flow/ClusterFlowChecker.java:91,102-107, ClusterParamFlowChecker.java:77-79, RLS SimpleClusterFlowChecker.java:49-61),

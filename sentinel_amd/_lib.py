@@ -129,6 +129,17 @@ class SgaBlockRow(C.Structure):  # sga_block_row: one aggregated key of the bloc
                 ("tag_kind", C.c_uint8), ("reserved", C.c_uint8 * 6)]
 
 
+class SgaMetricResRow(C.Structure):  # sga_metric_res_row: one resource's metric extension sums
+    _fields_ = [("pass_", C.c_int64), ("pass_events", C.c_int64), ("success", C.c_int64), ("exits", C.c_int64),
+                ("exception", C.c_int64), ("exception_events", C.c_int64), ("rt_sum", C.c_int64),
+                ("rt_max", C.c_int64), ("resource", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SgaMetricBlockRow(C.Structure):  # sga_metric_block_row: one (resource, origin, decision, detail) block sum
+    _fields_ = [("block", C.c_int64), ("block_events", C.c_int64), ("resource", C.c_uint32), ("origin", C.c_uint32),
+                ("detail", C.c_uint32), ("decision", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 class SgaCbEvent(C.Structure):  # sga_cb_event: one circuit breaker transition
     _fields_ = [("ts", C.c_int64), ("value", C.c_double), ("seq", C.c_uint64), ("resource", C.c_uint32),
                 ("breaker", C.c_uint32), ("epoch", C.c_uint32), ("sub", C.c_uint16), ("prev", C.c_uint8),
@@ -288,6 +299,10 @@ SIGNATURES = {
     "sga_block_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_block_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "sga_metric_ext_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "sga_metric_ext_drain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p,
+                                       C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_int64)]),
     "sga_server_log_enable": (C.c_int, [C.c_void_p, C.c_uint32]),
     "sga_server_log_drain": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),

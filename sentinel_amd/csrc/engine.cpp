@@ -2969,6 +2969,24 @@ int sga_block_log_drain(sga_engine *e, int64_t before_ms, sga_block_row *rows, s
     });
 }
 
+int sga_metric_ext_enable(sga_engine *e, uint32_t max_block_rows) {
+    return guarded(e, [&](Engine &g) {
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.metric_ext_enable(max_block_rows);
+    });
+}
+
+int sga_metric_ext_drain(sga_engine *e, sga_metric_res_row *res_rows, size_t res_cap, size_t *n_res,
+                         sga_metric_block_row *block_rows, size_t block_cap, size_t *n_block, uint64_t *lost_events,
+                         int64_t *lost_count) {
+    static_assert(sizeof(sga_metric_res_row) == 72 && sizeof(sga_metric_block_row) == 32, "metric extension rows");
+    return guarded(e, [&](Engine &g) {  // guarded first decides the events waiting in the queue
+        SGA_HIP_CHECK(hipSetDevice(g.cfg.device));
+        return g.flow.metric_ext_drain(res_rows, res_cap, n_res, block_rows, block_cap, n_block, lost_events,
+                                       lost_count);
+    });
+}
+
 int sga_server_log_enable(sga_engine *e, uint32_t max_rows) {
     return guarded(e, [&](Engine &g) {
         SGA_HIP_CHECK(hipSetDevice(g.cfg.device));

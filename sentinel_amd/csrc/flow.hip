@@ -1618,6 +1618,296 @@ __global__ __launch_bounds__(kT) void k_blog_rebuild(BlogTab from, BlogTab to, u
         }
 }
 
+// ---- metric extensions (MetricEntryCallback / MetricExitCallback behind StatisticSlot.java:65-175, as sums)
+// What an event adds to its resource's line: nothing, a pass, an exit, an exit with an error, a revoke
+enum : int { kMxNone = 0, kMxIsPass, kMxIsExit, kMxIsError, kMxIsRevoke };
+
+// The claim word of a block row: a mix of (origin << 32 | resource, decision << 32 | detail), never 0
+__device__ __forceinline__ uint64_t mx_hash(uint64_t w0, uint64_t w1) {
+    const uint64_t h = splitmix64(splitmix64(w0) ^ w1);
+    return h ? h : 1ull;
+}
+
+// One lane's own event as the eight sums of a line
+__device__ __forceinline__ void mx_own(int cls, int64_t a, int64_t rt, int64_t (&g)[8]) {
+    const bool ex = cls == kMxIsExit || cls == kMxIsError;
+    g[kMxPass] = cls == kMxIsPass ? a : cls == kMxIsRevoke ? -a : 0;
+    g[kMxPassEv] = cls == kMxIsPass ? 1 : cls == kMxIsRevoke ? -1 : 0;
+    g[kMxSuccess] = ex ? a : 0;
+    g[kMxExits] = ex ? 1 : 0;
+    g[kMxExc] = cls == kMxIsError ? a : 0;
+    g[kMxExcEv] = cls == kMxIsError ? 1 : 0;
+    g[kMxRtSum] = ex ? rt : 0;
+    g[kMxRtMax] = ex && rt > 0 ? rt : 0;
+}
+
+// The lanes marked `same` combined into one line's sums, wave-uniform and in registers only: the event counts are
+// popcounts of ballots, the acquire and rt sums DPP scans, and a class no lane of the group holds costs no scan.
+// Every lane of the wave calls it.
+__device__ __forceinline__ void mx_group(bool same, int cls, int64_t a, int64_t rt, int64_t (&g)[8]) {
+    const bool ex = same && (cls == kMxIsExit || cls == kMxIsError), er = same && cls == kMxIsError;
+    const unsigned long long mp = __ballot(same && cls == kMxIsPass), mr = __ballot(same && cls == kMxIsRevoke);
+    const unsigned long long mx = __ballot(ex), me = __ballot(er);
+    for (int j = 0; j < 8; ++j) g[j] = 0;
+    if (mp | mr) {
+        g[kMxPass] = wave_sum_i64(same ? (cls == kMxIsPass ? a : cls == kMxIsRevoke ? -a : 0) : 0);
+        g[kMxPassEv] = (int64_t)__popcll(mp) - (int64_t)__popcll(mr);
+    }
+    if (mx) {
+        g[kMxSuccess] = wave_sum_i64(ex ? a : 0);
+        g[kMxExits] = (int64_t)__popcll(mx);
+        g[kMxRtSum] = wave_sum_i64(ex ? rt : 0);
+        g[kMxRtMax] = wave_max_i64(ex ? rt : 0);
+    }
+    if (me) {
+        g[kMxExc] = wave_sum_i64(er ? a : 0);
+        g[kMxExcEv] = (int64_t)__popcll(me);
+    }
+}
+
+// One lane adds combined sums to a resource's line: a zero field costs nothing, and nothing is read back
+__device__ __forceinline__ void mx_res_add(const MxTab &tb, uint32_t r, const int64_t (&g)[8]) {
+    long long *p = tb.res[r].v;
+    for (int j = 0; j < kMxRtMax; ++j)
+        if (g[j]) atomicAdd((unsigned long long *)p + j, (unsigned long long)g[j]);
+    if (g[kMxRtMax] > 0) atomicMax(p + kMxRtMax, (long long)g[kMxRtMax]);
+}
+
+// One lane adds a wave's combined (sum of acquire, events) to a block key's row, as blog_update does: linear probing
+// from the hash, a free slot claimed by one compare-and-swap whose winner stores the key fields (never the sums,
+// which others may already be adding to), a slot holding the same hash shared, no waiting; a key that finds
+// neither within the probe limit goes to the lost counters.
+__device__ __forceinline__ void mx_block_add(const MxTab &tb, uint64_t w0, uint64_t w1, uint64_t h, int64_t sum,
+                                             int64_t cnt) {
+    const uint32_t limit = min(tb.mask + 1u, kBlogProbe);
+    uint32_t s = (uint32_t)(h >> 20) & tb.mask;
+    for (uint32_t p = 0; p < limit; ++p, s = (s + 1u) & tb.mask) {
+        unsigned long long cur = __atomic_load_n(&tb.hash[s], __ATOMIC_RELAXED);
+        if (cur == 0ull) {
+            cur = atomicCAS(&tb.hash[s], 0ull, (unsigned long long)h);
+            if (cur == 0ull) {
+                sga_metric_block_row &r = tb.row[s];
+                r.resource = (uint32_t)w0;
+                r.origin = (uint32_t)(w0 >> 32);
+                r.detail = (uint32_t)w1;
+                r.decision = (uint8_t)(w1 >> 32);
+                cur = h;
+            }
+        }
+        if (cur == h) {
+            atomicAdd((unsigned long long *)&tb.row[s].block, (unsigned long long)sum);
+            atomicAdd((unsigned long long *)&tb.row[s].block_events, (unsigned long long)cnt);
+            return;
+        }
+    }
+    atomicAdd(&tb.ctl[0], (unsigned long long)cnt);
+    atomicAdd(&tb.ctl[1], (unsigned long long)sum);
+}
+
+// The chunk's last stage when the sums are on: one lane an event, grid-stride over whole blocks (every lane of a wave
+// stays in the loop: the combines are wave-wide).  By the caller's kind and the final decision an event adds to its
+// resource's line (a pass, an exit, a revoke), forms a block key (a block, a kind 2 / 3 event), both (a revoke) or
+// nothing (an unknown resource, a refused chunk's -1).  Unlike the block log most lanes contribute, so the wave
+// combines by resource before touching memory, as k_blog_add does by tuple: the first pending lane's resource is
+// broadcast, the lanes sharing it are summed in registers (mx_group), and after the loop the first lanes of all the
+// resources update their lines side by side.  A resource that at least two lanes share can become the wave's held
+// resource: its eight sums stay wave-uniform over the wave's later tiles, which merge into it first, and reach the
+// line once, at the end or when a resource with more lanes in a tile takes its place -- a chunk of passes and exits
+// on one resource costs at most eight atomics a wave.  The block keys go the same way with a held key of their own.
+__global__ __launch_bounds__(kT) void k_mx_add(MxTab tb, const uint8_t *__restrict__ kind_in,
+                                               const uint32_t *__restrict__ resource,
+                                               const int32_t *__restrict__ acquire,
+                                               const uint8_t *__restrict__ flags, const int64_t *__restrict__ rt_in,
+                                               const uint32_t *__restrict__ origin,
+                                               const int8_t *__restrict__ decision,
+                                               const int32_t *__restrict__ wait_ms, uint32_t n) {
+    const int lane = (int)(threadIdx.x & 63u);
+    // the held resource and the held block key: everything wave-uniform, written out by lane 0
+    bool held = false, bheld = false;
+    uint32_t hr = 0;
+    int64_t hv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t bh = 0, bw0 = 0, bw1 = 0;
+    int64_t bsum = 0, bcnt = 0;
+    for (uint32_t i0 = blockIdx.x * kT; i0 < n; i0 += gridDim.x * kT) {
+        const uint32_t i = i0 + threadIdx.x;
+        int cls = kMxNone;
+        bool hasb = false;
+        uint32_t r = 0;
+        int64_t a = 0, rt = 0;
+        uint64_t w0 = 0, w1 = 0, h = 0;
+        if (i < n) {
+            const int8_t d = decision[i];
+            r = resource[i];
+            if (d >= 0 && r < tb.nres) {
+                const uint8_t kd = kind_in[i];
+                a = (int64_t)acquire[i];
+                if (kd == SGA_KIND_ENTRY) {
+                    if (d == SGA_PASS || d == SGA_PASS_WAIT) {
+                        cls = kMxIsPass;
+                    } else if (d == SGA_BLOCK_FLOW || d == SGA_BLOCK_PARAM || d == SGA_BLOCK_DEGRADE ||
+                               d == SGA_BLOCK_SYSTEM || d == SGA_BLOCK_AUTHORITY) {
+                        hasb = true;
+                        w1 = (uint64_t)(uint8_t)d << 32 | (uint32_t)wait_ms[i];
+                    }
+                } else if (kd == SGA_KIND_EXIT) {
+                    cls = (flags[i] & SGA_EV_ERROR) ? kMxIsError : kMxIsExit;
+                    rt = rt_in[i];
+                } else if (kd == SGA_KIND_BLOCKED) {
+                    hasb = true;
+                } else if (kd == SGA_KIND_REVOKE) {
+                    hasb = true;
+                    cls = kMxIsRevoke;
+                }
+                if (hasb) {
+                    w0 = (uint64_t)(origin ? origin[i] : 0u) << 32 | r;
+                    h = mx_hash(w0, w1);
+                }
+            }
+        }
+        // ---- the lines, by resource
+        bool has = cls != kMxNone;
+        unsigned long long pend = __ballot(has);
+        uint32_t hm = 0;  // lanes of this tile that merged into the held resource
+        if (held && pend) {
+            const bool same = has && r == hr;
+            const unsigned long long sm = __ballot(same);
+            if (sm) {
+                int64_t g[8];
+                mx_group(same, cls, a, rt, g);
+                for (int j = 0; j < kMxRtMax; ++j) hv[j] += g[j];
+                if (g[kMxRtMax] > hv[kMxRtMax]) hv[kMxRtMax] = g[kMxRtMax];
+                hm = (uint32_t)__popcll(sm);
+                has = has && !same;
+                pend &= ~sm;
+            }
+        }
+        bool first = false;  // this lane is the first of a resource that goes to its line after the loop
+        int64_t own[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        while (pend) {
+            const int lead = __ffsll(pend) - 1;
+            const uint32_t lr = (uint32_t)__builtin_amdgcn_readlane((int)r, lead);
+            const bool same = has && r == lr;
+            const unsigned long long sm = __ballot(same);
+            const uint32_t cnt = (uint32_t)__popcll(sm);
+            if (cnt >= 2) {  // wave-uniform
+                int64_t g[8];
+                mx_group(same, cls, a, rt, g);
+                if (cnt > hm) {  // the resource becomes the held one, the old one goes out
+                    if (held && lane == 0) mx_res_add(tb, hr, hv);
+                    held = true;
+                    hr = lr;
+                    for (int j = 0; j < 8; ++j) hv[j] = g[j];
+                    hm = cnt;
+                } else if (lane == lead) {
+                    first = true;
+                    for (int j = 0; j < 8; ++j) own[j] = g[j];
+                }
+            } else if (lane == lead) {
+                first = true;
+                mx_own(cls, a, rt, own);
+            }
+            has = has && !same;
+            pend &= ~sm;
+        }
+        if (first) mx_res_add(tb, r, own);
+        // ---- the block rows, by key
+        pend = __ballot(hasb);
+        hm = 0;
+        if (bheld && pend) {
+            const bool same = hasb && h == bh;
+            const unsigned long long sm = __ballot(same);
+            if (sm) {
+                bsum += wave_sum_i64(same ? a : 0);
+                hm = (uint32_t)__popcll(sm);
+                bcnt += hm;
+                hasb = hasb && !same;
+                pend &= ~sm;
+            }
+        }
+        first = false;
+        int64_t gsum = 0, gcnt = 0;
+        while (pend) {
+            const int lead = __ffsll(pend) - 1;
+            const uint64_t lh = (uint64_t)readlane_i64((int64_t)h, lead);
+            const bool same = hasb && h == lh;
+            const unsigned long long sm = __ballot(same);
+            const uint32_t cnt = (uint32_t)__popcll(sm);
+            if (cnt >= 2) {  // wave-uniform
+                const int64_t sum = wave_sum_i64(same ? a : 0);
+                if (cnt > hm) {
+                    if (bheld && lane == 0) mx_block_add(tb, bw0, bw1, bh, bsum, bcnt);
+                    bheld = true;
+                    bh = lh;
+                    bw0 = (uint64_t)readlane_i64((int64_t)w0, lead);
+                    bw1 = (uint64_t)readlane_i64((int64_t)w1, lead);
+                    bsum = sum;
+                    bcnt = hm = cnt;
+                } else if (lane == lead) {
+                    first = true;
+                    gsum = sum;
+                    gcnt = cnt;
+                }
+            } else if (lane == lead) {
+                first = true;
+                gsum = a;
+                gcnt = 1;
+            }
+            hasb = hasb && !same;
+            pend &= ~sm;
+        }
+        if (first) mx_block_add(tb, w0, w1, h, gsum, gcnt);
+    }
+    if (lane == 0) {
+        if (held) mx_res_add(tb, hr, hv);
+        if (bheld) mx_block_add(tb, bw0, bw1, bh, bsum, bcnt);
+    }
+}
+
+// Drain: the resources with any non-zero sum and every claimed block row compacted into the two output buffers in
+// one launch, nothing removed.  A wave appends together: one atomic on the counter per wave and table, the lanes'
+// places from the ballot.  out_res holds nres rows, out_block `slots`.
+__global__ __launch_bounds__(kT) void k_mx_drain(MxTab tb, uint32_t slots, sga_metric_res_row *out_res,
+                                                 sga_metric_block_row *out_block, uint32_t *count) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63u);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    MxRes L{};
+    bool has = false;
+    if (i < tb.nres) {
+        L = tb.res[i];
+        for (int j = 0; j < 8; ++j) has = has || L.v[j] != 0;
+    }
+    unsigned long long m = __ballot(has);
+    if (m) {  // wave-uniform
+        const int lead = __ffsll(m) - 1;
+        uint32_t base = 0;
+        if (lane == lead) base = atomicAdd(&count[0], (uint32_t)__popcll(m));
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, lead);
+        if (has) {
+            sga_metric_res_row &o = out_res[base + (uint32_t)__popcll(m & below)];
+            o.pass = L.v[kMxPass];
+            o.pass_events = L.v[kMxPassEv];
+            o.success = L.v[kMxSuccess];
+            o.exits = L.v[kMxExits];
+            o.exception = L.v[kMxExc];
+            o.exception_events = L.v[kMxExcEv];
+            o.rt_sum = L.v[kMxRtSum];
+            o.rt_max = L.v[kMxRtMax];
+            o.resource = i;
+            o.reserved = 0;
+        }
+    }
+    has = i < slots && tb.hash[i] != 0ull;
+    m = __ballot(has);
+    if (m) {
+        const int lead = __ffsll(m) - 1;
+        uint32_t base = 0;
+        if (lane == lead) base = atomicAdd(&count[1], (uint32_t)__popcll(m));
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, lead);
+        if (has) out_block[base + (uint32_t)__popcll(m & below)] = tb.row[i];
+    }
+}
+
 __global__ void k_lseq(FlowState st, int64_t max_rt, SysDev sys, const uint8_t *__restrict__ kind,
                        const uint32_t *__restrict__ resource, const uint32_t *__restrict__ ts_off, int64_t ts_base,
                        const int32_t *__restrict__ acquire, const uint8_t *__restrict__ flags,
@@ -8035,6 +8325,7 @@ int FlowEngine::submit_small(Chunk c, const uint8_t *kind, const uint32_t *resou
     SGA_HIP_CHECK(hipGetLastError());
     chunk_epilogue(c, true);
     block_log_pass(c);
+    metric_ext_pass(c);
     SGA_HIP_CHECK(hipStreamSynchronize(c.s));
     std::memcpy(decision, h + o_dec, m);
     if (wait_ms) std::memcpy(wait_ms, h + o_wait, 4 * m);
@@ -8246,6 +8537,7 @@ int FlowEngine::submit(const uint8_t *kind, const uint32_t *resource, const int6
                 else chunk_pipeline(c, has_in);
                 chunk_epilogue(c, false);
                 block_log_pass(c);
+                metric_ext_pass(c);
                 SGA_HIP_CHECK(hipMemcpyAsync(decision + b, d_dec.p, m, hipMemcpyDeviceToHost, stream));
                 if (wait_ms) SGA_HIP_CHECK(hipMemcpyAsync(wait_ms + b, d_wait.p, m * 4, hipMemcpyDeviceToHost, stream));
                 uint32_t ovf = 0;
@@ -8351,6 +8643,7 @@ int FlowEngine::submit_device(const uint8_t *d_kind_in, const uint32_t *d_resour
                        c.wait_ms);
     SGA_HIP_CHECK(hipGetLastError());
     block_log_pass(c);  // after k_lfail: a refused chunk answers -1 and logs nothing
+    metric_ext_pass(c);
     seq += n;
     if (cbev.on) cbev.seq += n;
     return 0;
@@ -8942,6 +9235,100 @@ int FlowEngine::block_log_drain(int64_t before_ms, sga_block_row *rows, size_t c
         if (x.origin != y.origin) return x.origin < y.origin;
         if (x.tag_kind != y.tag_kind) return x.tag_kind < y.tag_kind;
         return x.tag < y.tag;
+    });
+    return 0;
+}
+
+// ---- metric extensions
+// Counts what a drain would return (counts[0] resource rows, [1] block rows) into the output buffers; removes nothing
+void FlowEngine::metric_ext_collect(uint32_t counts[2], unsigned long long lost[2]) {
+    const uint32_t nb = (std::max(nres, mext.slots) + kT - 1) / kT;
+    SGA_HIP_CHECK(hipMemsetAsync(mext.cnt.p, 0, 8, stream));
+    hipLaunchKernelGGL(k_mx_drain, dim3(nb), dim3(kT), 0, stream, metric_ext_tab(), mext.slots, mext.out_res.p,
+                       mext.out_block.p, mext.cnt.p);
+    SGA_HIP_CHECK(hipGetLastError());
+    SGA_HIP_CHECK(hipMemcpyAsync(counts, mext.cnt.p, 8, hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipMemcpyAsync(lost, mext.ctl.p, 16, hipMemcpyDeviceToHost, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+int FlowEngine::metric_ext_enable(uint32_t max_block_rows) {
+    if (!nres) return SGA_EINVAL;
+    if (max_block_rows == 0) max_block_rows = 1u << 16;  // the default: a choice, not a measurement
+    if (max_block_rows > (1u << 26)) return SGA_EINVAL;
+    uint32_t slots = 64;
+    while (slots < max_block_rows) slots <<= 1;
+    if (mext.on) {  // with nothing pending the block table may be resized
+        uint32_t counts[2];
+        unsigned long long lost[2];
+        metric_ext_collect(counts, lost);
+        if (counts[0] || counts[1] || lost[0] || lost[1]) return SGA_EINVAL;
+        if (slots == mext.slots) return 0;
+    }
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (!mext.res.p) {
+        mext.res.alloc(nres);
+        mext.out_res.alloc(nres);
+        mext.ctl.alloc(2);
+        mext.cnt.alloc(2);
+        SGA_HIP_CHECK(hipMemsetAsync(mext.res.p, 0, mext.res.bytes(), stream));
+        SGA_HIP_CHECK(hipMemsetAsync(mext.ctl.p, 0, mext.ctl.bytes(), stream));
+    }
+    mext.hash.alloc(slots);
+    mext.row.alloc(slots);
+    mext.out_block.alloc(slots);
+    SGA_HIP_CHECK(hipMemsetAsync(mext.hash.p, 0, mext.hash.bytes(), stream));
+    SGA_HIP_CHECK(hipMemsetAsync(mext.row.p, 0, mext.row.bytes(), stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    mext.slots = slots;
+    mext.on = true;
+    return 0;
+}
+
+// The last stage of a chunk on every entry, behind block_log_pass on the chunk's stream.  Nothing when the sums are
+// off.
+void FlowEngine::metric_ext_pass(const Chunk &c) {
+    if (!mext.on) return;
+    // four tiles a block and at most 512 blocks: a wave's held resource gathers what its tiles share
+    const uint32_t nb = std::min<uint32_t>((c.m + 4 * kT - 1) / (4 * kT), 512);
+    hipLaunchKernelGGL(k_mx_add, dim3(nb), dim3(kT), 0, c.s, metric_ext_tab(), c.kind_in, c.resource, c.acquire, c.flags,
+                       c.rt, c.ids[kPairOrigin], c.decision, c.wait_ms, c.m);
+    SGA_HIP_CHECK(hipGetLastError());
+}
+
+int FlowEngine::metric_ext_drain(sga_metric_res_row *res_rows, size_t res_cap, size_t *n_res,
+                                 sga_metric_block_row *block_rows, size_t block_cap, size_t *n_block,
+                                 uint64_t *lost_events, int64_t *lost_count) {
+    if (!mext.on || !n_res || !n_block || (res_cap && !res_rows) || (block_cap && !block_rows)) return SGA_EINVAL;
+    *n_res = *n_block = 0;
+    uint32_t counts[2] = {0, 0};
+    unsigned long long lost[2] = {0, 0};
+    metric_ext_collect(counts, lost);
+    *n_res = counts[0];
+    *n_block = counts[1];
+    if (counts[0] > res_cap || counts[1] > block_cap) return SGA_ERANGE;  // nothing removed, the lost counters kept
+    if (counts[0]) {
+        SGA_HIP_CHECK(hipMemcpyAsync(res_rows, mext.out_res.p, (size_t)counts[0] * sizeof(sga_metric_res_row),
+                                     hipMemcpyDeviceToHost, stream));
+        SGA_HIP_CHECK(hipMemsetAsync(mext.res.p, 0, mext.res.bytes(), stream));
+    }
+    if (counts[1]) {
+        SGA_HIP_CHECK(hipMemcpyAsync(block_rows, mext.out_block.p, (size_t)counts[1] * sizeof(sga_metric_block_row),
+                                     hipMemcpyDeviceToHost, stream));
+        SGA_HIP_CHECK(hipMemsetAsync(mext.hash.p, 0, mext.hash.bytes(), stream));
+        SGA_HIP_CHECK(hipMemsetAsync(mext.row.p, 0, mext.row.bytes(), stream));
+    }
+    if (lost[0] || lost[1]) SGA_HIP_CHECK(hipMemsetAsync(mext.ctl.p, 0, 16, stream));
+    SGA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (lost_events) *lost_events = lost[0];
+    if (lost_count) *lost_count = (int64_t)lost[1];
+    std::sort(res_rows, res_rows + counts[0],
+              [](const sga_metric_res_row &x, const sga_metric_res_row &y) { return x.resource < y.resource; });
+    std::sort(block_rows, block_rows + counts[1], [](const sga_metric_block_row &x, const sga_metric_block_row &y) {
+        if (x.resource != y.resource) return x.resource < y.resource;
+        if (x.origin != y.origin) return x.origin < y.origin;
+        if (x.decision != y.decision) return x.decision < y.decision;
+        return x.detail < y.detail;
     });
     return 0;
 }

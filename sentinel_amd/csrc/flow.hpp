@@ -211,6 +211,23 @@ struct BlogTab {
 constexpr uint32_t kBlogProbe = 128;  // linear probes before a tuple counts as lost
 constexpr uint8_t kBlogScalar = 0, kBlogList = 1;  // sga_block_row::tag_kind
 
+// Metric extensions (StatisticSlot's callbacks, sga_metric_ext_enable).  res: one 64-byte line of eight signed sums
+// per resource, in sga_metric_res_row's order (pass, pass_events, success, exits, exception, exception_events, rt_sum,
+// rt_max) -- dense, so it cannot overflow and the drain is one streaming scan.  The block rows live in an
+// open-addressing table claimed as the block log's is: hash[s] is a mix of (resource, origin, decision, detail),
+// never 0, and the only thing a lookup compares.  Integer atomics only; nobody waits for another wave.
+struct MxRes {
+    long long v[8];
+};
+enum : int { kMxPass = 0, kMxPassEv, kMxSuccess, kMxExits, kMxExc, kMxExcEv, kMxRtSum, kMxRtMax };
+struct MxTab {
+    MxRes *res;
+    unsigned long long *hash;
+    sga_metric_block_row *row;
+    unsigned long long *ctl;  // [0] lost_events [1] lost_count
+    uint32_t nres, mask;
+};
+
 // Breaker events (sga_cb_events_enable): an append buffer of sga_cb_event in HBM behind one atomic counter.  The
 // kernels that write a breaker's state append one record per transition (flow.hip cb_emit); a record that finds
 // the buffer full only counts in ctl[1].  The header lives in device memory (rewritten when the log is enabled or
@@ -585,6 +602,26 @@ struct FlowEngine {
     void block_log_pass(const Chunk &c);
     int block_log_drain(int64_t before_ms, sga_block_row *rows, size_t cap, size_t *n, uint64_t *lost_events,
                         int64_t *lost_count);
+    // Metric extensions (MxTab): off until metric_ext_enable -- no chunk launches or allocates anything for them
+    // before.  metric_ext_pass follows block_log_pass as the chunk's last stage on every entry; a drain copies out
+    // and zeroes everything, so the block table needs no second copy.
+    struct MetricExt {
+        bool on = false;
+        uint32_t slots = 0;
+        DevBuf<MxRes> res;
+        DevBuf<unsigned long long> hash, ctl;
+        DevBuf<sga_metric_block_row> row, out_block;
+        DevBuf<sga_metric_res_row> out_res;
+        DevBuf<uint32_t> cnt;  // [0] resource rows [1] block rows of the drain under way
+    } mext;
+    MxTab metric_ext_tab() const {
+        return MxTab{mext.res.p, mext.hash.p, mext.row.p, mext.ctl.p, nres, mext.slots - 1};
+    }
+    void metric_ext_collect(uint32_t counts[2], unsigned long long lost[2]);
+    int metric_ext_enable(uint32_t max_block_rows);
+    void metric_ext_pass(const Chunk &c);
+    int metric_ext_drain(sga_metric_res_row *res_rows, size_t res_cap, size_t *n_res, sga_metric_block_row *block_rows,
+                         size_t block_cap, size_t *n_block, uint64_t *lost_events, int64_t *lost_count);
     // Breaker events (CbLog): off until cb_events_enable -- no chunk launches or allocates anything for it.  The
     // deciding kernels append; the drain copies out and sorts by (seq, sub) on the host.
     struct CbEvents {

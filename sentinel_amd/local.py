@@ -341,7 +341,7 @@ class LocalSentinel:
 
     def __init__(self, engine: Engine, resources: Sequence[str], origins: Optional[Sequence[str]] = None,
                  max_origin_nodes: int = 0, contexts: Optional[Sequence[str]] = None, max_context_nodes: int = 0,
-                 tree: bool = False, block_log=False):
+                 tree: bool = False, block_log=False, metric_extensions=False):
         """origins: the caller names events may carry (ContextUtil.enter's origin), registered up front like
         the resources; None = no origin tracking.  max_origin_nodes sizes the engine's table of (resource,
         origin) nodes (0: the engine's default).  contexts: the context names events may carry
@@ -352,7 +352,11 @@ class LocalSentinel:
         default context (sentinel_default_context) appears in the tree only if the caller registers that name and
         submits its entries with that id: context 0 stays untracked.  block_log: True (the engine's default of 65,536
         rows) or a row count turns on the engine's block log (LogSlot: sga_block_log_enable); block_rows drains it
-        and block_log.BlockLogWriter writes sentinel-block.log from it."""
+        and block_log.BlockLogWriter writes sentinel-block.log from it.  metric_extensions: True (the engine's default
+        of 65,536 block rows) or a block-row capacity turns on the engine's metric extension sums
+        (StatisticSlot's callbacks: sga_metric_ext_enable); `metric_extensions` is then the registry of
+        metric_extension.MetricExtension objects, metric_ext_rows drains the sums and poll_metric_extensions
+        drains and dispatches them."""
         self.engine = engine
         if tree and not contexts:
             raise ValueError("tree=True needs registered contexts")
@@ -402,6 +406,14 @@ class LocalSentinel:
             rows = 0 if block_log is True else int(block_log)
             check(_lib.load().sga_block_log_enable(engine.handle, rows), engine.handle, "blockLogEnable")
             self.block_log_rows = max(64, 1 << (rows - 1).bit_length()) if rows else 1 << 16
+        self.metric_ext_block_rows = 0  # 0: the metric extension sums are off
+        self.metric_extensions = None
+        if metric_extensions:
+            from .metric_extension import MetricExtensionProvider
+            rows = 0 if metric_extensions is True else int(metric_extensions)
+            check(_lib.load().sga_metric_ext_enable(engine.handle, rows), engine.handle, "metricExtEnable")
+            self.metric_ext_block_rows = max(64, 1 << (rows - 1).bit_length()) if rows else 1 << 16
+            self.metric_extensions = MetricExtensionProvider()
 
     def context_id(self, name: str) -> int:
         """Dense id of a registered context; "" is 0 (no tracked context)."""
@@ -777,6 +789,37 @@ class LocalSentinel:
         check(_lib.load().sga_block_log_drain(self.engine.handle, before, out.ctypes.data, cap, C.byref(n),
                                               C.byref(le), C.byref(lc)), self.engine.handle, "blockLogDrain")
         return out[:n.value].copy(), int(le.value), int(lc.value)
+
+    # ---- metric extensions (StatisticSlot's callbacks)
+    def metric_ext_rows(self):
+        """sga_metric_ext_drain: (res_rows, block_rows, lost_events, lost_count) -- everything summed since the last
+        drain.  res_rows: a metric_extension.METRIC_RES_ROW_DTYPE array of the resources with any non-zero sum, sorted
+        by resource; block_rows: a METRIC_BLOCK_ROW_DTYPE array sorted by (resource, origin, decision, detail); the
+        lost counters: blocked entries, and their acquire sum, that found no room in the block table.  The sums are
+        signed deltas: a revoke drained apart from its entry shows as a negative pass."""
+        from .metric_extension import METRIC_BLOCK_ROW_DTYPE, METRIC_RES_ROW_DTYPE
+        if not self.metric_ext_block_rows:
+            raise ValueError("metric_ext_rows needs LocalSentinel(metric_extensions=...)")
+        rcap, bcap = len(self.resources), self.metric_ext_block_rows
+        res = np.zeros(max(1, rcap), dtype=METRIC_RES_ROW_DTYPE)
+        blk = np.zeros(max(1, bcap), dtype=METRIC_BLOCK_ROW_DTYPE)
+        nr, nb, le, lc = C.c_size_t(), C.c_size_t(), C.c_uint64(), C.c_int64()
+        check(_lib.load().sga_metric_ext_drain(self.engine.handle, res.ctypes.data, rcap, C.byref(nr),
+                                               blk.ctypes.data, bcap, C.byref(nb), C.byref(le), C.byref(lc)),
+              self.engine.handle, "metricExtDrain")
+        return res[:nr.value].copy(), blk[:nb.value].copy(), int(le.value), int(lc.value)
+
+    def poll_metric_extensions(self) -> int:
+        """Drains the sums and hands them to the registered extensions (metric_extension.dispatch: resource order,
+        registration order, the reference's order inside each callback).  Returns the number of calls made; with no
+        extension registered nothing is drained."""
+        from .metric_extension import dispatch
+        if self.metric_extensions is None:
+            raise ValueError("poll_metric_extensions needs LocalSentinel(metric_extensions=...)")
+        if not len(self.metric_extensions):
+            return 0
+        res, blk, le, lc = self.metric_ext_rows()
+        return dispatch(self, self.metric_extensions, res, blk, le, lc)
 
     def node(self, resource, now: int) -> NodeView:
         """ClusterNode views; resource ENTRY_NODE (or TOTAL_IN_RESOURCE_NAME) is Constants.ENTRY_NODE."""
